@@ -20,9 +20,18 @@ The JSON line carries:
                  (MI355X_MICROARCH.md). traffic: measured HBM bytes/launch
                  from a committed rocprofv3 --pmc summary (profiles/), with
                  the gfx950 FETCH_SIZE ×2 correction, else null.
-  cpu_baseline — the CPU oracle (kind "port": the reference executor
-                 restated, scalar, 1 thread) timed on this host on a bounded
-                 sample of the same workload.
+  cpu_baseline — --full only (null in a plain run): the CPU oracle (kind
+                 "port": the reference executor restated, scalar, 1 thread)
+                 timed on this host on a bounded sample of the same workload.
+
+A plain run stages, warms up, times --steps steps and prints the line.
+--full adds the legs that take runs of their own (today: cpu_baseline and
+the vs_baseline derived from it). --dump-outputs DIR writes what the last
+timed step returned to its caller as DIR/<name>.npy (float64). The inputs
+are seeded and identical from run to run; keys, counts and integer-valued
+sums reproduce exactly, the float8 SUM/AVG columns to the last ulp or two
+(measured ≤ 1e-15 relative: the kernels combine block partials with atomics,
+so the f64 summation order is not fixed).
 """
 import argparse
 import ctypes as C
@@ -107,6 +116,32 @@ def cpu_baseline(query, sample_rows, shards=1):
     }
 
 
+def outputs_as_arrays(workload, out):
+    """The value the timed path returned to its caller, as named float64
+    arrays. Group rows (Q1/Q9: list of dicts; Q3: structured top-k array)
+    become one array per column in row order; single-character keys are
+    stored as their code point. Every integer here (counts, orderkeys,
+    dates) is far below 2^53, so float64 holds it exactly."""
+    import numpy as np
+    if workload == "scan_count":
+        return {"count": np.array([out], dtype=np.float64)}
+    if workload == "tpch_q3":
+        return {f: np.ascontiguousarray(out[f], dtype=np.float64)
+                for f in out.dtype.names}
+    cols = {}
+    for r in out:
+        for k, v in r.items():
+            cols.setdefault(k, []).append(ord(v) if isinstance(v, str) else v)
+    return {k: np.array(v, dtype=np.float64) for k, v in cols.items()}
+
+
+def dump_outputs(dirname, workload, out):
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in outputs_as_arrays(workload, out).items():
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -117,7 +152,14 @@ def main():
     ap.add_argument("--workload", default="tpch_q1",
                     choices=["tpch_q1", "scan_count", "tpch_q3",
                              "tpch_q9mix"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure "
+                         "(cpu_baseline / vs_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as "
+                         "DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--skew", action="store_true",
                     help="config-5 skewed distribution keys (hot custkeys)")
     ap.add_argument("--cpu-sample-rows", type=int, default=1_200_000_000,
@@ -253,10 +295,14 @@ def main():
 
     barrier_sync()
     t_start = time.time()
+    last_out = None
     for _ in range(args.steps):
-        step()
+        last_out = step()
     barrier_sync()
     elapsed = time.time() - t_start
+
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, args.workload, last_out)
 
     # MAX over ranks
     if dist is not None:
@@ -300,7 +346,7 @@ def main():
         }
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline \
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1 \
             and args.workload in ("tpch_q1", "tpch_q3", "tpch_q9mix"):
         log("running cpu_baseline (oracle port, 1 core)...")
         q = {"tpch_q1": "q1", "tpch_q3": "q3",

@@ -50,6 +50,44 @@ def test_committed_bench_snapshots_schema():
         assert 0 < d["roofline"]["frac"] < 1
 
 
+def test_dump_outputs_group_rows(tmp_path):
+    """--dump-outputs: group rows (the Q1/Q9 step result) become one float64
+    array per column, row order kept, character keys as code points."""
+    import numpy as np
+    b = _bench()
+    rows = [{"l_returnflag": "A", "l_linestatus": "F", "sum_qty": 1.5,
+             "count_order": 600_000_001},
+            {"l_returnflag": "N", "l_linestatus": "O", "sum_qty": 2.25,
+             "count_order": 7}]
+    d = tmp_path / "out"
+    b.dump_outputs(str(d), "tpch_q1", rows)
+    assert sorted(os.listdir(d)) == ["count_order.npy", "l_linestatus.npy",
+                                     "l_returnflag.npy", "sum_qty.npy"]
+    for f in os.listdir(d):
+        assert np.load(d / f).dtype == np.float64
+    assert np.load(d / "count_order.npy").tolist() == [600_000_001, 7]
+    assert np.load(d / "l_returnflag.npy").tolist() == [ord("A"), ord("N")]
+    assert np.load(d / "sum_qty.npy").tolist() == [1.5, 2.25]
+
+
+def test_dump_outputs_topk_and_scalar():
+    """The Q3 step result (structured top-k rows) dumps field by field; the
+    scan_count result is a 1-element array."""
+    import numpy as np
+    b = _bench()
+    dt = np.dtype([("l_orderkey", "i8"), ("revenue", "f8"),
+                   ("o_orderdate", "i4"), ("o_shippriority", "i4")])
+    top = np.array([(3_000_000_007, 9.5, 2400, 0), (11, 8.25, 2399, 0)],
+                   dtype=dt)
+    a = b.outputs_as_arrays("tpch_q3", top)
+    assert set(a) == set(dt.names)
+    assert all(v.dtype == np.float64 and v.shape == (2,) for v in a.values())
+    assert a["l_orderkey"].tolist() == [3_000_000_007, 11]
+    assert a["revenue"].tolist() == [9.5, 8.25]
+    c = b.outputs_as_arrays("scan_count", 123_456_789)
+    assert c["count"].dtype == np.float64 and c["count"].tolist() == [123_456_789]
+
+
 def test_cpu_baseline_sharded():
     """shards>1 = one CLI process per shard (DataNode deployment analog):
     whole-job rows/s over max-shard time, cores = shards, and roughly

@@ -7,11 +7,11 @@ set -x
 mkdir -p gpurun_out
 
 # 1. headline benches with CPU baselines (scalar, 1 core)
-timeout 300 python bench.py --steps 20 --warmup 5 \
+timeout 300 python bench.py --full --steps 20 --warmup 5 \
     > gpurun_out/m_q1.json 2> gpurun_out/m_q1.err; echo q1=$?
-timeout 300 python bench.py --workload tpch_q3 --steps 15 --warmup 4 \
+timeout 300 python bench.py --full --workload tpch_q3 --steps 15 --warmup 4 \
     > gpurun_out/m_q3.json 2> gpurun_out/m_q3.err; echo q3=$?
-timeout 300 python bench.py --workload tpch_q9mix --steps 15 --warmup 4 \
+timeout 300 python bench.py --full --workload tpch_q9mix --steps 15 --warmup 4 \
     > gpurun_out/m_q9.json 2> gpurun_out/m_q9.err; echo q9=$?
 
 # 2. all-cores CPU baselines (one oracle process per shard; SURVEY §8d both
