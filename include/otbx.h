@@ -32,6 +32,9 @@
  *                            operators for generic plan shapes (+ NULL
  *                            semantics parity: execGrouping.c:295 NULL==NULL
  *                            grouping; nodeHash.c:2026 NULL keys dropped)
+ *   otbx_agg_i64_var       — HashAggregate carrying the full float8_accum
+ *                            state [N,Sx,Sxx] (float.c:2823) for var_pop /
+ *                            var_samp / stddev_pop / stddev_samp
  *   merge (Coordinator)    — NOT here: the shard merge (execFragment.c:3877)
  *                            is a collective over ranks, done by the host
  *                            layer with RCCL (torch.distributed) on the
@@ -315,6 +318,41 @@ otbx_status otbx_agg_i64(const int64_t *keys_dev, const uint8_t *key_null_dev,
                          int64_t n, void *ws_dev, size_t ws_bytes,
                          otbx_agg_group *groups_dev, int64_t *ngroups_dev,
                          void *stream);
+
+/* Variance/stddev aggregate: the full float8_accum transition state
+ * [N, Sx, Sxx] (utils/adt/float.c:2823) per group, feeding var_pop /
+ * var_samp / stddev_pop / stddev_samp (float.c:3011-3096; finalizers in the
+ * host layer). Grouping contract identical to otbx_agg_i64: NULL keys form
+ * one group, the INT64_MIN-valued key is supported, NULL values are skipped
+ * by count_v/sum_v/sxx and counted by count_star, n == 0 gives zero groups,
+ * emission order is arbitrary, groups_dev capacity = n.
+ * Numerics: sxx is NOT sum(x^2) - Sx^2/N (that form cancels
+ * catastrophically once |mean| >> stddev). The call runs otbx_agg_i64 for
+ * N and Sx, then a second pass accumulates d = x - Sx/N per row and emits
+ * sxx = sum(d^2) - sum(d)^2/N, which stays within the float8 parity bar of
+ * the reference's Youngs-Cramer recurrence.
+ *   count_v == 1            -> sxx == 0
+ *   group holds Inf or NaN  -> sxx == NaN
+ *   otherwise sxx >= 0 (a negative rounding residue is clamped to 0).
+ * Overflow of FINITE inputs is not detected (the reference raises "value
+ * out of range: overflow"): like otbx_agg_i64 the call has no device-to-host
+ * error channel; an overflowed Sx or Sxx reads back as Inf / NaN. */
+typedef struct {
+    int64_t key;
+    int64_t count_star;
+    int64_t count_v;     /* = N of the float8_accum state */
+    double  sum_v;       /* = Sx */
+    double  sxx;         /* = Sxx = sum((x - mean)^2), >= 0 or NaN */
+    int32_t key_isnull;
+    int32_t sum_isnull;  /* count_v == 0: the whole state is SQL NULL */
+} otbx_var_group;        /* 48 B */
+
+otbx_status otbx_agg_i64_var_workspace_bytes(int64_t n, size_t *bytes);
+otbx_status otbx_agg_i64_var(const int64_t *keys_dev, const uint8_t *key_null_dev,
+                             const double *vals_dev, const uint8_t *val_null_dev,
+                             int64_t n, void *ws_dev, size_t ws_bytes,
+                             otbx_var_group *groups_dev, int64_t *ngroups_dev,
+                             void *stream);
 
 /* ---- extended join types + two-key variants ----
  * The HJ_* fill-state FSM (executor/nodeHashjoin.c:139-144) on the generic

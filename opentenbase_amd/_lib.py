@@ -94,6 +94,7 @@ def lib():
         # compute entry points keep the explicit-ctypes call style)
         i64, u32, szp = C.c_int64, C.c_uint32, C.POINTER(C.c_size_t)
         _lib.otbx_agg_i64_workspace_bytes.argtypes = [i64, szp]
+        _lib.otbx_agg_i64_var_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_join_i64_workspace_bytes.argtypes = [i64, i64, szp]
         _lib.otbx_order_groups_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_q3_workspace_bytes.argtypes = [i64, i64, i64, szp]
@@ -122,6 +123,7 @@ EXPORTED_SYMBOLS = [
     "otbx_topk_by_revenue",
     "otbx_order_groups_workspace_bytes", "otbx_order_groups",
     "otbx_agg_i64_workspace_bytes", "otbx_agg_i64",
+    "otbx_agg_i64_var_workspace_bytes", "otbx_agg_i64_var",
     "otbx_partition_by_key", "otbx_gather_i64", "otbx_gather_f64",
     "otbx_gather_i32", "otbx_gather_u8",
     "otbx_join_i64_workspace_bytes", "otbx_join_i64",

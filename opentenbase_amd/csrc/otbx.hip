@@ -17,8 +17,10 @@
  *   hash aggregate  execGrouping.c:295, simplehash.h (open addressing),
  *                   nodeAgg.c:856/2609
  *   transition fns  int8inc int8.c:714, float8pl float.c:970,
- *                   float8_accum float.c:2823 (GPU keeps [N,Sx]; Sxx /
- *                   variance is out of scope — DESIGN.md §3)
+ *                   float8_accum float.c:2823 ([N,Sx] in every aggregate;
+ *                   the full [N,Sx,Sxx] state in otbx_agg_i64_var, by a
+ *                   corrected two-pass sum of squared deviations — the
+ *                   additive sum(x^2) form cancels)
  *   NULL semantics  strict transfns skip NULL (nodeAgg.c:743), NULL group
  *                   keys equal (execGrouping.c:520), NULL join keys never
  *                   match (nodeHash.c:2026)
@@ -1770,10 +1772,21 @@ otbx_status otbx_agg_i64_workspace_bytes(int64_t n, size_t *bytes)
     return OTBX_OK;
 }
 
-otbx_status otbx_agg_i64(const int64_t *keys, const uint8_t *knull,
-                         const double *vals, const uint8_t *vnull, int64_t n,
-                         void *ws, size_t ws_bytes, otbx_agg_group *out,
-                         int64_t *ngroups_dev, void *stream)
+/* what the partitioned direct path leaves behind in the workspace: the
+ * (key,val) records grouped into key-disjoint buckets. otbx_agg_i64_var
+ * runs its second pass over them; nbuckets == 0 = another path was taken */
+struct agg_part_layout {
+    const ulonglong2 *recs;
+    const unsigned long long *offs, *cnts;
+    const uint8_t *flags; /* 1 = bucket overflowed its LDS table */
+    uint32_t nbuckets;
+};
+
+static otbx_status agg_i64_run(const int64_t *keys, const uint8_t *knull,
+                               const double *vals, const uint8_t *vnull,
+                               int64_t n, void *ws, size_t ws_bytes,
+                               otbx_agg_group *out, int64_t *ngroups_dev,
+                               void *stream, agg_part_layout *lay)
 {
     int64_t cap = next_pow2_host(n < 16 ? 16 : (int64_t)(n / 0.7) + 1);
     {
@@ -1956,6 +1969,13 @@ otbx_status otbx_agg_i64(const int64_t *keys, const uint8_t *knull,
                                        foffs, fcnts, flags, tab, cap);
                     compact_tab = true;
                 }
+                if (lay) {
+                    lay->recs = frecs;
+                    lay->offs = foffs;
+                    lay->cnts = fcnts;
+                    lay->flags = flags;
+                    lay->nbuckets = fgrid;
+                }
             }
         } else {
             hipLaunchKernelGGL(k_aggp_scatter, dim3(grid_for(n, 256)),
@@ -2020,6 +2040,392 @@ otbx_status otbx_agg_i64(const int64_t *keys, const uint8_t *knull,
     else
         hipLaunchKernelGGL(k_agg_emit_specials, dim3(1), dim3(64), 0, s,
                            nullgrp, out, ngroups_dev);
+    HIP_CHECK(hipGetLastError());
+    return OTBX_OK;
+}
+
+otbx_status otbx_agg_i64(const int64_t *keys, const uint8_t *knull,
+                         const double *vals, const uint8_t *vnull, int64_t n,
+                         void *ws, size_t ws_bytes, otbx_agg_group *out,
+                         int64_t *ngroups_dev, void *stream)
+{
+    return agg_i64_run(keys, knull, vals, vnull, n, ws, ws_bytes, out,
+                       ngroups_dev, stream, nullptr);
+}
+
+} /* extern "C" */
+
+/* ============ variance aggregate (otbx_agg_i64_var) ============
+ * The full float8_accum state [N, Sx, Sxx] (float.c:2823). Sxx has no
+ * accurate additive one-pass form (sum(x^2) - Sx^2/N cancels: 4e-4 relative
+ * at mean 1e6 / stddev 1), so this is two passes over the input:
+ *   pass 1  otbx_agg_i64, unchanged, into a scratch group array -> N, Sx
+ *   index   key -> {mean = Sx/N, acc} open-addressing table over the
+ *           COMPACTED groups (sized from ngroups, not n), staged in the
+ *           then-dead pass-1 table region; NULL-key and AGG_EMPTY-key
+ *           groups get the two dedicated slots after it (as nullgrp[0..1])
+ *   pass 2  per row d = x - mean(group); accumulate sum(d^2) and sum(d):
+ *           bucket-resident over pass 1's partitioned records when the
+ *           direct path ran (k_var_bucket_pass2), else streamed with
+ *           pre-aggregation in a per-block LDS table keyed by slot index
+ *           (k_var_pass2, the k_agg_build recipe: hot keys never reach
+ *           global atomics)
+ *   final   Sxx = sum(d^2) - sum(d)^2/N   (corrected two-pass: the second
+ *           term removes the rounding error of the mean), clamped at 0.
+ * Inf/NaN inputs make mean, d and both sums non-finite, and Inf - Inf = NaN
+ * lands Sxx on NaN as float8_accum does. A one-row group has d == 0
+ * exactly. */
+struct var_slot {
+    long long key;
+    double mean;
+    double sd2; /* sum(d^2) */
+    double sd;  /* sum(d)   */
+};
+
+#define VAR_LDS_SLOTS 512
+#define VAR_LDS_PROBES 4
+
+struct var_lds_slot {
+    long long si; /* index slot; -1 = empty */
+    double sd2, sd;
+};
+
+__global__ __launch_bounds__(256) void k_var_init(var_slot *tab, int64_t cap)
+{
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < cap;
+         i += stride) {
+        tab[i].key = AGG_EMPTY;
+        tab[i].mean = 0.0;
+        tab[i].sd2 = 0.0;
+        tab[i].sd = 0.0;
+    }
+}
+
+/* insert the compacted pass-1 groups (unique keys: one writer per slot) */
+__global__ __launch_bounds__(256) void
+k_var_index(const otbx_agg_group *__restrict__ g, int64_t ng, var_slot *tab,
+            int64_t cap)
+{
+    int64_t mask = cap - 1;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < ng;
+         i += stride) {
+        double mean =
+            g[i].count_v > 0 ? g[i].sum_v / (double)g[i].count_v : 0.0;
+        int64_t k = g[i].key;
+        if (g[i].key_isnull) {
+            tab[cap].mean = mean;
+            continue;
+        }
+        if (k == AGG_EMPTY) {
+            tab[cap + 1].mean = mean;
+            continue;
+        }
+        int64_t s = (int64_t)(d_hash_i64(k) & (uint64_t)mask);
+        for (int64_t t = 0; t <= mask; t++) {
+            long long old = atomicCAS((unsigned long long *)&tab[s].key,
+                                      (unsigned long long)AGG_EMPTY,
+                                      (unsigned long long)k);
+            if (old == AGG_EMPTY) {
+                tab[s].mean = mean;
+                break;
+            }
+            s = (s + 1) & mask;
+        }
+    }
+}
+
+/* read-only lookup (the index was built by an earlier launch); bounded so a
+ * missing key ends the probe instead of spinning */
+__device__ __forceinline__ int64_t d_var_find(const var_slot *tab,
+                                              int64_t mask, int64_t k)
+{
+    int64_t s = (int64_t)(d_hash_i64(k) & (uint64_t)mask);
+    for (int64_t t = 0; t <= mask; t++) {
+        long long kk = tab[s].key;
+        if (kk == k) return s;
+        if (kk == AGG_EMPTY) return -1;
+        s = (s + 1) & mask;
+    }
+    return -1;
+}
+
+__global__ __launch_bounds__(256) void
+k_var_pass2(const int64_t *__restrict__ keys,
+            const uint8_t *__restrict__ knull,
+            const double *__restrict__ vals,
+            const uint8_t *__restrict__ vnull, int64_t n, var_slot *tab,
+            int64_t cap, bool specials_only)
+{
+    __shared__ var_lds_slot ltab[VAR_LDS_SLOTS];
+    for (int s = threadIdx.x; s < VAR_LDS_SLOTS; s += blockDim.x) {
+        ltab[s].si = -1;
+        ltab[s].sd2 = 0.0;
+        ltab[s].sd = 0.0;
+    }
+    __syncthreads();
+    int64_t mask = cap - 1;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        if (vnull && vnull[i]) continue; /* strict transfn skips NULL */
+        int64_t k = keys[i];
+        bool kn = knull && knull[i];
+        /* the bucket pass covers ordinary keys; this launch then only
+         * sweeps up the two dedicated groups */
+        if (specials_only && !kn && k != AGG_EMPTY) continue;
+        int64_t si = kn                ? cap
+                     : k == AGG_EMPTY ? cap + 1
+                                      : d_var_find(tab, mask, k);
+        if (si < 0) continue; /* unreachable: pass 1 saw every key */
+        double d = vals[i] - tab[si].mean;
+        double d2 = d * d;
+        int s = (int)(d_hash_i64(si) & (uint64_t)(VAR_LDS_SLOTS - 1));
+        bool placed = false;
+        for (int t = 0; t < VAR_LDS_PROBES; t++) {
+            long long old = atomicCAS((unsigned long long *)&ltab[s].si,
+                                      (unsigned long long)-1ll,
+                                      (unsigned long long)si);
+            if (old == -1ll || old == si) {
+                atomicAdd(&ltab[s].sd2, d2);
+                atomicAdd(&ltab[s].sd, d);
+                placed = true;
+                break;
+            }
+            s = (s + 1) & (VAR_LDS_SLOTS - 1);
+        }
+        if (!placed) { /* LDS window full: spill straight to global */
+            atomicAdd(&tab[si].sd2, d2);
+            atomicAdd(&tab[si].sd, d);
+        }
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < VAR_LDS_SLOTS; s += blockDim.x) {
+        long long si = ltab[s].si;
+        if (si >= 0) {
+            atomicAdd(&tab[si].sd2, ltab[s].sd2);
+            atomicAdd(&tab[si].sd, ltab[s].sd);
+        }
+    }
+}
+
+/* bucket-resident pass 2 over the records the partitioned direct path of
+ * pass 1 left in the workspace. Buckets hold DISJOINT key sets and fit one
+ * LDS table (k_aggp_bucket_agg_kv_direct's sizing and probe sequence), so
+ * the per-row work never leaves LDS: scattered global f64 atomics run at
+ * ~22 G/s chip-wide, which bound the generic pass at 11 Grows/s.
+ *   A  insert the bucket's keys into the LDS table
+ *   B  one index lookup per DISTINCT key -> mean
+ *   C  second sweep of the records: d = v - mean into LDS sum(d^2), sum(d)
+ *   D  one global add per distinct key
+ * A bucket that pass 1 flagged, or whose table overflows here, takes the
+ * generic per-row route for its own rows. */
+#define VARB_LSLOTS 1024
+
+struct varb_lds_slot {
+    long long key;
+    double mean, sd2, sd;
+};
+
+__device__ __forceinline__ void d_var_row_global(var_slot *tab, int64_t mask,
+                                                 int64_t k, double v)
+{
+    int64_t si = d_var_find(tab, mask, k);
+    if (si < 0) return;
+    double d = v - tab[si].mean;
+    atomicAdd(&tab[si].sd2, d * d);
+    atomicAdd(&tab[si].sd, d);
+}
+
+__global__ __launch_bounds__(256) void
+k_var_bucket_pass2(const ulonglong2 *__restrict__ recs,
+                   const unsigned long long *__restrict__ offs,
+                   const unsigned long long *__restrict__ cnts,
+                   const uint8_t *__restrict__ flags, var_slot *tab,
+                   int64_t cap)
+{
+    __shared__ varb_lds_slot ltab[VARB_LSLOTS];
+    __shared__ int bfail;
+    int64_t mask = cap - 1;
+    int64_t lo = (int64_t)offs[blockIdx.x];
+    int64_t hi = lo + (int64_t)cnts[blockIdx.x];
+    if (threadIdx.x == 0) bfail = flags[blockIdx.x] ? 1 : 0;
+    for (int t = threadIdx.x; t < VARB_LSLOTS; t += blockDim.x) {
+        ltab[t].key = AGG_EMPTY;
+        ltab[t].mean = 0.0;
+        ltab[t].sd2 = 0.0;
+        ltab[t].sd = 0.0;
+    }
+    __syncthreads();
+    if (!bfail) { /* A (block-uniform: bfail was read after the barrier) */
+        for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+            int64_t k = (int64_t)recs[i].x;
+            if (k == AGG_EMPTY) continue; /* dedicated slot: specials sweep */
+            uint64_t h = d_hash_i64(k);
+            int t0 = (int)(h & (uint64_t)(VARB_LSLOTS - 1));
+            int step = (int)(((h >> 52) & (uint64_t)(VARB_LSLOTS - 2)) | 1ull);
+            bool placed = false;
+            for (int t = 0; t < 64; t++) {
+                long long old = atomicCAS((unsigned long long *)&ltab[t0].key,
+                                          (unsigned long long)AGG_EMPTY,
+                                          (unsigned long long)k);
+                if (old == AGG_EMPTY || old == k) {
+                    placed = true;
+                    break;
+                }
+                t0 = (t0 + step) & (VARB_LSLOTS - 1);
+            }
+            if (!placed) bfail = 1; /* any-lane plain store, read after the
+                                     * barrier */
+        }
+    }
+    __syncthreads();
+    if (bfail) { /* generic route for this bucket's rows */
+        for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+            ulonglong2 r = recs[i];
+            if ((int64_t)r.x == AGG_EMPTY) continue;
+            d_var_row_global(tab, mask, (int64_t)r.x,
+                             __longlong_as_double((long long)r.y));
+        }
+        return;
+    }
+    /* B: each thread owns the same LDS slots here and in D (256 threads:
+     * the launch and __launch_bounds__ agree), so the index slot stays in
+     * a register instead of being looked up twice */
+    int64_t sis[VARB_LSLOTS / 256];
+#pragma unroll
+    for (int j = 0; j < VARB_LSLOTS / 256; j++) {
+        int t = (int)threadIdx.x + j * 256;
+        long long k = ltab[t].key;
+        sis[j] = k == AGG_EMPTY ? -1 : d_var_find(tab, mask, k);
+        if (sis[j] >= 0) ltab[t].mean = tab[sis[j]].mean;
+    }
+    __syncthreads();
+    /* C: every key of the bucket is in the table, so the probe ends */
+    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+        ulonglong2 r = recs[i];
+        int64_t k = (int64_t)r.x;
+        if (k == AGG_EMPTY) continue;
+        uint64_t h = d_hash_i64(k);
+        int t0 = (int)(h & (uint64_t)(VARB_LSLOTS - 1));
+        int step = (int)(((h >> 52) & (uint64_t)(VARB_LSLOTS - 2)) | 1ull);
+        for (int t = 0; t < 64 && ltab[t0].key != k; t++)
+            t0 = (t0 + step) & (VARB_LSLOTS - 1);
+        if (ltab[t0].key != k) continue; /* unreachable */
+        double d = __longlong_as_double((long long)r.y) - ltab[t0].mean;
+        atomicAdd(&ltab[t0].sd2, d * d);
+        atomicAdd(&ltab[t0].sd, d);
+    }
+    __syncthreads();
+    /* D */
+#pragma unroll
+    for (int j = 0; j < VARB_LSLOTS / 256; j++) {
+        int t = (int)threadIdx.x + j * 256;
+        if (sis[j] < 0) continue;
+        atomicAdd(&tab[sis[j]].sd2, ltab[t].sd2);
+        atomicAdd(&tab[sis[j]].sd, ltab[t].sd);
+    }
+}
+
+__global__ __launch_bounds__(256) void
+k_var_finalize(const otbx_agg_group *__restrict__ g, int64_t ng,
+               const var_slot *__restrict__ tab, int64_t cap,
+               otbx_var_group *__restrict__ out)
+{
+    int64_t mask = cap - 1;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < ng;
+         i += stride) {
+        otbx_agg_group gi = g[i];
+        double sxx = 0.0;
+        if (gi.count_v > 0) {
+            int64_t si = gi.key_isnull          ? cap
+                         : gi.key == AGG_EMPTY ? cap + 1
+                                               : d_var_find(tab, mask, gi.key);
+            if (si < 0) {
+                sxx = __longlong_as_double(0x7ff8000000000000ll);
+            } else {
+                double sd2 = tab[si].sd2, sd = tab[si].sd;
+                sxx = sd2 - sd * sd / (double)gi.count_v;
+                if (sxx < 0.0) sxx = 0.0; /* rounding residue */
+                /* float8_accum never leaves Sxx infinite (float.c:2855) */
+                if (isinf(sxx)) sxx = __longlong_as_double(0x7ff8000000000000ll);
+            }
+        }
+        out[i].key = gi.key;
+        out[i].count_star = gi.count_star;
+        out[i].count_v = gi.count_v;
+        out[i].sum_v = gi.sum_v;
+        out[i].sxx = sxx;
+        out[i].key_isnull = gi.key_isnull;
+        out[i].sum_isnull = gi.sum_isnull;
+    }
+}
+
+static_assert(sizeof(otbx_var_group) == 48, "otbx_var_group ABI");
+static_assert(sizeof(var_slot) == sizeof(agg_slot),
+              "the index reuses the pass-1 table region slot for slot");
+
+extern "C" {
+
+otbx_status otbx_agg_i64_var_workspace_bytes(int64_t n, size_t *bytes)
+{
+    size_t a;
+    otbx_agg_i64_workspace_bytes(n, &a);
+    a = (a + 255) & ~(size_t)255;
+    /* + the pass-1 scratch groups (capacity n, as groups_dev) */
+    *bytes = a + (size_t)(n < 1 ? 1 : n) * sizeof(otbx_agg_group);
+    return OTBX_OK;
+}
+
+otbx_status otbx_agg_i64_var(const int64_t *keys, const uint8_t *knull,
+                             const double *vals, const uint8_t *vnull,
+                             int64_t n, void *ws, size_t ws_bytes,
+                             otbx_var_group *out, int64_t *ngroups_dev,
+                             void *stream)
+{
+    size_t need, a;
+    otbx_agg_i64_var_workspace_bytes(n, &need);
+    if (ws_bytes < need) return OTBX_ERR_INVALID;
+    otbx_agg_i64_workspace_bytes(n, &a);
+    hipStream_t s = (hipStream_t)stream;
+    otbx_agg_group *g1 =
+        (otbx_agg_group *)((char *)ws + ((a + 255) & ~(size_t)255));
+    /* pass 1: every existing path (LDS two-level, small table + redo,
+     * partitioned direct, NULL-carrying gather) -> count(*), N, Sx */
+    agg_part_layout lay = {};
+    otbx_status st = agg_i64_run(keys, knull, vals, vnull, n, ws, a, g1,
+                                 ngroups_dev, stream, &lay);
+    if (st != OTBX_OK || n == 0) return st;
+
+    static int64_t *h_ng = nullptr;
+    if (!h_ng) SCR_ALLOC_HOST(h_ng, 8);
+    HIP_CHECK(hipMemcpyAsync(h_ng, ngroups_dev, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    int64_t ng = *h_ng;
+    if (ng <= 0) return OTBX_OK;
+    if (ng > n) return OTBX_ERR_INVALID; /* cannot happen: capacity is n */
+
+    /* the pass-1 table region is dead now; ng <= n keeps the index inside
+     * it: (cap + 2) slots of the same 32 B */
+    int64_t cap = next_pow2_host(ng < 16 ? 16 : (int64_t)(ng / 0.7) + 1);
+    var_slot *tab = (var_slot *)ws;
+    hipLaunchKernelGGL(k_var_init, dim3(grid_for(cap + 2, 256)), dim3(256), 0,
+                       s, tab, cap + 2);
+    hipLaunchKernelGGL(k_var_index, dim3(grid_for(ng, 256)), dim3(256), 0, s,
+                       g1, ng, tab, cap);
+    /* the partition records sit past the pass-1 table region, which the
+     * index (cap <= pass-1 cap) never leaves */
+    if (lay.nbuckets)
+        hipLaunchKernelGGL(k_var_bucket_pass2, dim3(lay.nbuckets), dim3(256),
+                           0, s, lay.recs, lay.offs, lay.cnts, lay.flags, tab,
+                           cap);
+    hipLaunchKernelGGL(k_var_pass2, dim3(grid_for(n, 256)), dim3(256), 0, s,
+                       keys, knull, vals, vnull, n, tab, cap,
+                       lay.nbuckets != 0);
+    hipLaunchKernelGGL(k_var_finalize, dim3(grid_for(ng, 256)), dim3(256), 0,
+                       s, g1, ng, tab, cap, out);
     HIP_CHECK(hipGetLastError());
     return OTBX_OK;
 }

@@ -12,6 +12,7 @@ Device memory, streams: torch (plumbing only — all compute is in libotbx.so;
 there is NO torch/CPU fallback for any operator here).
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -574,6 +575,81 @@ class GpuHashAgg(CustomScanState):
         arr = out[: ngroups * 40].cpu().numpy().view(dt).copy()
         arr.sort(order=["key_isnull", "key"])
         return list(arr)
+
+
+VAR_GROUP_DTYPE = [("key", "i8"), ("count_star", "i8"), ("count_v", "i8"),
+                   ("sum_v", "f8"), ("sxx", "f8"),
+                   ("key_isnull", "i4"), ("sum_isnull", "i4")]
+
+
+class GpuHashAggVar(CustomScanState):
+    """HashAggregate carrying the full float8_accum state [N, Sx, Sxx]
+    (float.c:2823) per group — the partial state of var_pop / var_samp /
+    stddev_pop / stddev_samp over a float8 column. Grouping and NULL
+    semantics as GpuHashAgg; rows are otbx_var_group records sorted by
+    (key_isnull, key). Finalize with var_pop(N, Sxx) etc. below."""
+
+    def __init__(self, keys, vals, key_null=None, val_null=None):
+        super().__init__()
+        self.keys, self.vals = keys, vals
+        self.key_null, self.val_null = key_null, val_null
+
+    def _run(self):
+        import numpy as np
+        L = lib()
+        n = len(self.keys)
+        ws_bytes = C.c_size_t(0)
+        check(L.otbx_agg_i64_var_workspace_bytes(C.c_int64(n),
+                                                 C.byref(ws_bytes)))
+        ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8,
+                         device="cuda")
+        out = torch.empty(max(n, 1) * 48, dtype=torch.uint8, device="cuda")
+        ng = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+        def vp(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+
+        call("otbx_agg_i64_var", vp(self.keys), vp(self.key_null),
+             vp(self.vals), vp(self.val_null), C.c_int64(n),
+             C.c_void_p(ws.data_ptr()), C.c_size_t(ws_bytes.value),
+             C.c_void_p(out.data_ptr()), C.c_void_p(ng.data_ptr()), _stream())
+        ngroups = int(ng.cpu().item())
+        dt = np.dtype(VAR_GROUP_DTYPE)
+        arr = out[: ngroups * 48].cpu().numpy().view(dt).copy()
+        # (key_isnull, key) only: sxx may be NaN and must not take part
+        arr = arr[np.lexsort((arr["key"], arr["key_isnull"]))]
+        return list(arr)
+
+
+# float8 variance finalizers over the [N, Sx, Sxx] state (float.c:3011-3096).
+# None = SQL NULL. Sxx is non-negative (or NaN) by construction.
+
+def var_pop(N, Sxx):
+    """float8_var_pop (float.c:3011): NULL when N == 0."""
+    N, Sxx = float(N), float(Sxx)
+    if N == 0.0:
+        return None
+    return Sxx / N
+
+
+def var_samp(N, Sxx):
+    """float8_var_samp (float.c:3033): NULL when N <= 1."""
+    N, Sxx = float(N), float(Sxx)
+    if N <= 1.0:
+        return None
+    return Sxx / (N - 1.0)
+
+
+def stddev_pop(N, Sxx):
+    """float8_stddev_pop (float.c:3055): NULL when N == 0."""
+    v = var_pop(N, Sxx)
+    return None if v is None else math.sqrt(v)
+
+
+def stddev_samp(N, Sxx):
+    """float8_stddev_samp (float.c:3077): NULL when N <= 1."""
+    v = var_samp(N, Sxx)
+    return None if v is None else math.sqrt(v)
 
 
 class GpuHashAggDec(CustomScanState):

@@ -8,10 +8,13 @@ One process per GPU (1 DN shard â†” 1 GPU); collectives via torch.distributed â€
 backend "nccl" IS RCCL on ROCm (xGMI inside the node); CPU tests use "gloo"
 with the same code path.
 """
+import math
+
 import torch
 import torch.distributed as dist
 
-from .executor import q1_finalize, q1_rows_from_state
+from ._lib import OtbxError
+from .executor import VAR_GROUP_DTYPE, q1_finalize, q1_rows_from_state
 
 
 def is_dist():
@@ -103,6 +106,64 @@ def merge_q3_topk(candidates, k=10):
     order = np.lexsort((cands["l_orderkey"], cands["o_orderdate"],
                         -cands["revenue"]))
     return cands[order][:k]
+
+
+def combine_var_state(a, b):
+    """float8_combine (float.c:2725) on two [N, Sx, Sxx] transition states:
+    the generalised Youngs-Cramer merge, in the reference's operation order
+    (so the result is bit-identical to the C function). An empty side
+    (N == 0) returns the other unchanged. A finite-input overflow is an
+    error, as the reference's float_overflow_error()."""
+    N1, Sx1, Sxx1 = float(a[0]), float(a[1]), float(a[2])
+    N2, Sx2, Sxx2 = float(b[0]), float(b[1]), float(b[2])
+    if N1 == 0.0:
+        return (N2, Sx2, Sxx2)
+    if N2 == 0.0:
+        return (N1, Sx1, Sxx1)
+    N = N1 + N2
+    Sx = Sx1 + Sx2
+    if math.isinf(Sx) and not math.isinf(Sx1) and not math.isinf(Sx2):
+        raise OtbxError(4, "float8_combine: Sx overflow")
+    tmp = Sx1 / N1 - Sx2 / N2
+    Sxx = Sxx1 + Sxx2 + N1 * N2 * tmp * tmp / N
+    if math.isinf(Sxx) and not math.isinf(Sxx1) and not math.isinf(Sxx2):
+        raise OtbxError(4, "float8_combine: Sxx overflow")
+    return (N, Sx, Sxx)
+
+
+def merge_var_partials(rows):
+    """Coordinator merge of a grouped variance: all-gather every rank's
+    GpuHashAggVar rows (otbx_var_group records, as raw bytes â€” the
+    merge_q3_topk pattern), then combine rows of equal (key_isnull, key) in
+    rank order: float8_combine on [count_v, sum_v, sxx], int8pl on
+    count_star. Returns rows sorted like the node's output. With one rank
+    or no process group the input is returned as is."""
+    if not is_dist() or dist.get_world_size() == 1:
+        return rows
+    import numpy as np
+    dt = np.dtype(VAR_GROUP_DTYPE)
+    local = np.array([tuple(r[f] for f in dt.names) for r in rows], dtype=dt)
+    raw = torch.from_numpy(local.view(np.uint8).reshape(-1).copy())
+    dev = "cuda" if torch.cuda.is_available() and \
+        dist.get_backend() == "nccl" else "cpu"
+    raw = raw.to(dev)
+    allraw = allgather_variable(raw).cpu().numpy().tobytes()
+    parts = np.frombuffer(allraw, dtype=dt)
+    merged = {}  # (key_isnull, key) -> [count_star, (N, Sx, Sxx)]
+    for r in parts:                       # concatenation is in rank order
+        ident = (int(r["key_isnull"]), int(r["key"]))
+        st = (float(r["count_v"]), float(r["sum_v"]), float(r["sxx"]))
+        m = merged.get(ident)
+        if m is None:
+            merged[ident] = [int(r["count_star"]), st]
+        else:
+            m[0] += int(r["count_star"])
+            m[1] = combine_var_state(m[1], st)
+    out = np.zeros(len(merged), dtype=dt)
+    for i, ident in enumerate(sorted(merged)):
+        cs, (N, Sx, Sxx) = merged[ident]
+        out[i] = (ident[1], cs, int(N), Sx, Sxx, ident[0], int(N == 0.0))
+    return list(out)
 
 
 def finalize_q1(rows):

@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
 """Scale benchmark of the generic composable operators (otbx_agg_i64 /
-otbx_join_i64) — arbitrary-plan building blocks, distinct from the fused
-query pipelines."""
+otbx_agg_i64_var / otbx_join_i64) — arbitrary-plan building blocks,
+distinct from the fused query pipelines.
+
+  generic_ops_bench.py             agg + join shapes
+  generic_ops_bench.py --agg-var   agg and agg_var at the same three shapes
+                                   in one process (profiles/agg_var_ops.txt)
+"""
 import ctypes as C
+import os
 import sys
 import time
 
 import torch
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from opentenbase_amd import executor as ex  # noqa: E402
 from opentenbase_amd._lib import call, lib  # noqa: E402
 
@@ -37,6 +43,41 @@ def bench_agg(n, ngroups):
         best = min(best, time.time() - t0)
     print(f"agg  n={n:>11_} groups={ngroups:>9_}: {best*1e3:8.2f} ms "
           f"({n/best/1e9:6.1f} Grows/s), ngroups={int(ng.cpu().item())}")
+    return best
+
+
+def bench_agg_var(n, ngroups):
+    """otbx_agg_i64_var on bench_agg's input (same seed, same keys/values):
+    pass 1 is the otbx_agg_i64 call timed above, so time(agg_var) /
+    time(agg) prices the index build + second pass + finalize."""
+    g = torch.Generator(device="cuda").manual_seed(1)
+    keys = torch.randint(0, ngroups, (n,), dtype=torch.int64, device="cuda",
+                         generator=g)
+    vals = torch.rand(n, dtype=torch.float64, device="cuda", generator=g)
+    L = lib()
+    ws_bytes = C.c_size_t(0)
+    L.otbx_agg_i64_var_workspace_bytes(C.c_int64(n), C.byref(ws_bytes))
+    ws = torch.empty(ws_bytes.value, dtype=torch.uint8, device="cuda")
+    out = torch.empty(n * 48, dtype=torch.uint8, device="cuda")
+    ng = torch.zeros(1, dtype=torch.int64, device="cuda")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def run():
+        call("otbx_agg_i64_var", C.c_void_p(keys.data_ptr()), None,
+             C.c_void_p(vals.data_ptr()), None, C.c_int64(n),
+             C.c_void_p(ws.data_ptr()), C.c_size_t(ws_bytes.value),
+             C.c_void_p(out.data_ptr()), C.c_void_p(ng.data_ptr()), stream)
+        torch.cuda.synchronize()
+
+    run()  # warm-up (lazy scratch, code-object load)
+    best = 1e9
+    for _ in range(5):
+        t0 = time.time()
+        run()
+        best = min(best, time.time() - t0)
+    print(f"agg_var n={n:>11_} groups={ngroups:>9_}: {best*1e3:8.2f} ms "
+          f"({n/best/1e9:6.1f} Grows/s), ngroups={int(ng.cpu().item())}")
+    return best
 
 
 def bench_join(nb, np_):
@@ -153,6 +194,15 @@ def bench_round2_ops():
 
 if __name__ == "__main__":
     ex.init_device(0)
+    if "--agg-var" in sys.argv:
+        for groups in (4, 1_000_000, 100_000_000):
+            t_agg = bench_agg(600_000_000, groups)
+            torch.cuda.empty_cache()
+            t_var = bench_agg_var(600_000_000, groups)
+            torch.cuda.empty_cache()
+            print(f"agg_var / agg time ratio at groups={groups:_}: "
+                  f"{t_var / t_agg:.2f}")
+        sys.exit(0)
     bench_agg(600_000_000, 4)
     bench_agg(600_000_000, 1_000_000)
     bench_agg(600_000_000, 100_000_000)
