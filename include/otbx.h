@@ -35,6 +35,9 @@
  *   otbx_agg_i64_var       — HashAggregate carrying the full float8_accum
  *                            state [N,Sx,Sxx] (float.c:2823) for var_pop /
  *                            var_samp / stddev_pop / stddev_samp
+ *   otbx_sort_perm         — the Sort node for any tuple shape: ExecSort
+ *                            (executor/nodeSort.c:49) → tuplesort.c, with
+ *                            the bounded top-N of a Limit above it
  *   merge (Coordinator)    — NOT here: the shard merge (execFragment.c:3877)
  *                            is a collective over ranks, done by the host
  *                            layer with RCCL (torch.distributed) on the
@@ -496,6 +499,59 @@ otbx_status otbx_order_groups_workspace_bytes(int64_t n, size_t *bytes);
 otbx_status otbx_order_groups(const otbx_q3_group *groups_dev, int64_t n,
                               otbx_q3_group *out_dev, void *ws,
                               size_t ws_bytes, void *stream);
+
+/* ---- generic GPU Sort: multi-column ORDER BY [LIMIT k] ----
+ * The ExecSort → tuplesort analog (executor/nodeSort.c:49,
+ * utils/sort/tuplesort.c; bounded top-N of tuplesort_set_bound :1471) for
+ * any tuple shape: up to OTBX_MAX_KEYS key columns of type int64, float64,
+ * int32 or uint8, each with its own direction, NULL placement and optional
+ * null mask. The result is a PERMUTATION: perm_dev[j] is the input row
+ * index of the j-th output row, int64 so it feeds otbx_gather_* unchanged.
+ *
+ * limit == 0: full sort; capacity of perm_dev and *nout_dev are n.
+ * limit  > 0: LIMIT k; capacity and *nout_dev are min(limit, n), and the
+ *             result equals the first `limit` entries of the full sort.
+ * limit  < 0: invalid.
+ *
+ * ORDERING CONTRACT (ApplySortComparator, include/utils/sortsupport.h:201):
+ *   - key[0] is the primary key; key[i+1] breaks ties of key[0..i].
+ *   - Per key, two NULLs compare equal. A NULL sorts before every non-NULL
+ *     iff OTBX_SORT_NULLS_FIRST is set — independently of OTBX_SORT_DESC,
+ *     which (as ssup_reverse) only negates the comparison of two non-NULLs.
+ *   - I64, I32, U8: ordinary signed / signed / unsigned order (btint8cmp,
+ *     nbtcompare.c:129).
+ *   - F64: float8_cmp_internal (utils/adt/float.c:1172): every NaN equals
+ *     every other NaN — whatever its sign bit or payload — and is greater
+ *     than every non-NaN, +Inf included; -0.0 == +0.0.
+ *   - The value stored under a NULL is ignored entirely.
+ *   - The sort is STABLE: rows that compare equal on all keys keep input
+ *     order (the reference's qsort promises less; stability makes the
+ *     permutation unique, so parity is bit-exact).
+ *
+ * Stream-ordered, no host synchronisation and no device-to-host channel
+ * (like otbx_order_groups). Checked before any HIP call, each returning
+ * OTBX_ERR_INVALID: nkeys outside 1..8, a type code outside 0..3, flags
+ * outside bits 0-1, n < 0, n > INT32_MAX (row indices are 32-bit
+ * internally), limit < 0, a NULL col with n > 0, ws_bytes below
+ * otbx_sort_workspace_bytes(n, nkeys, limit). n == 0 is valid and writes
+ * *nout_dev = 0. otbx_sort_workspace_bytes is pure host code, monotone in
+ * n and in nkeys. */
+enum { OTBX_SORT_I64 = 0, OTBX_SORT_F64 = 1, OTBX_SORT_I32 = 2, OTBX_SORT_U8 = 3 };
+#define OTBX_SORT_DESC        1
+#define OTBX_SORT_NULLS_FIRST 2
+typedef struct {
+    const void    *col;     /* device column of `type`                      */
+    const uint8_t *nulls;   /* byte per row, nonzero = NULL; may be NULL    */
+    int32_t        type;    /* OTBX_SORT_*                                  */
+    int32_t        flags;   /* OTBX_SORT_DESC | OTBX_SORT_NULLS_FIRST       */
+} otbx_sortkey;
+typedef struct { int32_t nkeys; otbx_sortkey key[OTBX_MAX_KEYS]; } otbx_sortspec;
+
+otbx_status otbx_sort_workspace_bytes(int64_t n, int32_t nkeys, int64_t limit,
+                                      size_t *bytes);
+otbx_status otbx_sort_perm(const otbx_sortspec *spec, int64_t n, int64_t limit,
+                           void *ws_dev, size_t ws_bytes,
+                           int64_t *perm_dev, int64_t *nout_dev, void *stream);
 
 /* ---- repartition exchange ----
  * The GPU half of the reference's "Distribute results by H: col" exchange

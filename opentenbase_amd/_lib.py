@@ -65,6 +65,17 @@ class KeysetDev(C.Structure):
                 ("nulls", C.c_void_p * 8)]
 
 
+class SortKeyDev(C.Structure):
+    """otbx_sortkey (include/otbx.h)."""
+    _fields_ = [("col", C.c_void_p), ("nulls", C.c_void_p),
+                ("type", C.c_int32), ("flags", C.c_int32)]
+
+
+class SortSpecDev(C.Structure):
+    """otbx_sortspec: up to 8 sort keys, key[0] primary."""
+    _fields_ = [("nkeys", C.c_int32), ("key", SortKeyDev * 8)]
+
+
 class PartDev(C.Structure):
     _fields_ = [
         ("n", C.c_int64),
@@ -99,6 +110,7 @@ def lib():
         _lib.otbx_order_groups_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_q3_workspace_bytes.argtypes = [i64, i64, i64, szp]
         _lib.otbx_q9_workspace_bytes.argtypes = [i64, i64, i64, u32, szp]
+        _lib.otbx_sort_workspace_bytes.argtypes = [i64, C.c_int32, i64, szp]
     return _lib
 
 
@@ -132,4 +144,5 @@ EXPORTED_SYMBOLS = [
     "otbx_agg_i64_dec_workspace_bytes", "otbx_agg_i64_dec",
     "otbx_agg_i64n_workspace_bytes", "otbx_agg_i64n",
     "otbx_join_i64n_workspace_bytes", "otbx_join_i64n",
+    "otbx_sort_workspace_bytes", "otbx_sort_perm",
 ]

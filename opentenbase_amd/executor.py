@@ -17,7 +17,7 @@ import math
 import torch
 
 from ._lib import (CustomerDev, KeysetDev, LineitemDev, OrdersDev,
-                   OtbxError, PartDev, call, check, lib)
+                   OtbxError, PartDev, SortSpecDev, call, check, lib)
 
 Q1_SLOT_ORDER = [(b"A", b"F"), (b"A", b"O"), (b"N", b"F"),
                  (b"N", b"O"), (b"R", b"F"), (b"R", b"O")]
@@ -542,6 +542,108 @@ def gather(src, perm):
          C.c_void_p(perm.data_ptr()), C.c_int64(len(perm)),
          C.c_void_p(dst.data_ptr()), _stream())
     return dst
+
+
+SORT_DESC = 1          # OTBX_SORT_DESC
+SORT_NULLS_FIRST = 2   # OTBX_SORT_NULLS_FIRST
+_SORT_TYPE = {torch.int64: 0, torch.float64: 1, torch.int32: 2, torch.uint8: 3}
+
+
+def sort_flags(nkeys, descending=None, nulls_first=None):
+    """Per-key OTBX_SORT_* flag words. An unspecified nulls_first (None, or
+    None for one key) takes the SQL default: NULLS LAST for ASC, NULLS FIRST
+    for DESC (the parser's SORTBY_NULLS_DEFAULT rule, parse_clause.c)."""
+    desc = [False] * nkeys if descending is None else list(descending)
+    nf = [None] * nkeys if nulls_first is None else list(nulls_first)
+    if len(desc) != nkeys or len(nf) != nkeys:
+        raise OtbxError(3, "sort: one descending/nulls_first entry per key")
+    out = []
+    for d, f in zip(desc, nf):
+        if f is None:
+            f = bool(d)
+        out.append((SORT_DESC if d else 0) | (SORT_NULLS_FIRST if f else 0))
+    return out
+
+
+class GpuSort(CustomScanState):
+    """The Sort node (nodeSort.c:49 → tuplesort.c) over 1..8 key columns
+    (device tensors of dtype int64, float64, int32 or uint8): per-key
+    direction, NULL placement and optional null mask (uint8, nonzero =
+    NULL), optional LIMIT. Stable; ordering contract in include/otbx.h
+    (otbx_sort_perm). Yields ONE tuple: the int64 permutation tensor (row j
+    of the output is input row perm[j]); gather(col) applies it to a payload
+    column through the native gather kernels."""
+
+    def __init__(self, keys, descending=None, nulls_first=None, nulls=None,
+                 limit=0):
+        super().__init__()
+        self.keys = list(keys)
+        nk = len(self.keys)
+        if not 1 <= nk <= 8:
+            raise OtbxError(3, "sort: 1..8 keys")
+        for k in self.keys:
+            if k.dtype not in _SORT_TYPE:
+                raise OtbxError(3, f"sort: unsupported key dtype {k.dtype}")
+            if len(k) != len(self.keys[0]):
+                raise OtbxError(3, "sort: key columns differ in length")
+        self.nulls = [None] * nk if nulls is None else list(nulls)
+        if len(self.nulls) != nk:
+            raise OtbxError(3, "sort: one nulls entry per key")
+        self.flags = sort_flags(nk, descending, nulls_first)
+        self.limit = int(limit)
+        self.n = len(self.keys[0])
+        self.perm = None
+        self.sort_ms = None
+
+    def spec(self):
+        """The otbx_sortspec handed to otbx_sort_perm."""
+        sp = SortSpecDev()
+        sp.nkeys = len(self.keys)
+        for c, k in enumerate(self.keys):
+            sp.key[c].col = k.data_ptr()
+            nt = self.nulls[c]
+            sp.key[c].nulls = nt.data_ptr() if nt is not None else None
+            sp.key[c].type = _SORT_TYPE[k.dtype]
+            sp.key[c].flags = self.flags[c]
+        return sp
+
+    def _run(self):
+        L = lib()
+        n, nk = self.n, len(self.keys)
+        ws_bytes = C.c_size_t(0)
+        check(L.otbx_sort_workspace_bytes(C.c_int64(n), C.c_int32(nk),
+                                          C.c_int64(self.limit),
+                                          C.byref(ws_bytes)),
+              "otbx_sort_workspace_bytes")
+        ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8,
+                         device="cuda")
+        cap = min(self.limit, n) if self.limit > 0 else n
+        perm = torch.empty(max(cap, 1), dtype=torch.int64, device="cuda")
+        nout = torch.zeros(1, dtype=torch.int64, device="cuda")
+        sp = self.spec()
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        call("otbx_sort_perm", C.byref(sp), C.c_int64(n),
+             C.c_int64(self.limit), C.c_void_p(ws.data_ptr()),
+             C.c_size_t(ws_bytes.value), C.c_void_p(perm.data_ptr()),
+             C.c_void_p(nout.data_ptr()), _stream())
+        ev1.record()
+        k = int(nout.cpu().item())
+        self.sort_ms = ev0.elapsed_time(ev1)
+        self.perm = perm[:k]
+        return [self.perm]
+
+    def gather(self, col):
+        """col reordered by the sort (runs the node if it has not run)."""
+        if self.perm is None:
+            self.perm = self._run()[0]
+        return gather(col, self.perm)
+
+    def explain(self):
+        if self.sort_ms is None:
+            return None
+        return {"sort": self.sort_ms}
 
 
 class GpuHashAgg(CustomScanState):

@@ -108,6 +108,88 @@ def merge_q3_topk(candidates, k=10):
     return cands[order][:k]
 
 
+def _sort_norm_host(col, flags, null):
+    """numpy restatement of the device key normalisation of otbx_sort_perm
+    (DESIGN.md §8g.1): returns (null digit u8, radix key u64) whose
+    ascending order is the column's ORDER BY order."""
+    import numpy as np
+    a = np.ascontiguousarray(col)
+    top = np.uint64(1 << 63)
+    if a.dtype == np.int64:
+        k, mask = a.view(np.uint64) ^ top, np.uint64(0xffffffffffffffff)
+    elif a.dtype == np.float64:
+        b = a.view(np.uint64).copy()
+        b[np.isnan(a)] = np.uint64(0x7ff8000000000000)  # one NaN, above +Inf
+        b[a == 0] = np.uint64(0)                        # -0 == +0
+        k = np.where((b >> np.uint64(63)) != 0, ~b, b ^ top)
+        mask = np.uint64(0xffffffffffffffff)
+    elif a.dtype == np.int32:
+        k = (a.view(np.uint32) ^ np.uint32(0x80000000)).astype(np.uint64)
+        mask = np.uint64(0xffffffff)
+    elif a.dtype == np.uint8:
+        k, mask = a.astype(np.uint64), np.uint64(0xff)
+    else:
+        raise OtbxError(3, f"sort: unsupported key dtype {a.dtype}")
+    if flags & 1:                                       # OTBX_SORT_DESC
+        k = k ^ mask
+    isnull = np.zeros(len(a), dtype=bool) if null is None \
+        else np.asarray(null) != 0
+    k = np.where(isnull, np.uint64(0), k)
+    nfirst = bool(flags & 2)                            # OTBX_SORT_NULLS_FIRST
+    nd = np.where(isnull, 0 if nfirst else 1, 1 if nfirst else 0)
+    return nd.astype(np.uint8), k
+
+
+def merge_sorted_partials(key_cols, payload_cols, descending=None,
+                          nulls_first=None, nulls=None, limit=0):
+    """Coordinator merge of sorted DataNode streams (the merge-sorted recv of
+    execFragment.c:4035-4059). Every rank passes its locally sorted rows
+    (already cut to `limit` if set): key columns, payload columns and the
+    optional per-key null masks, as 1-D tensors. They are all-gathered in
+    rank order and ordered globally — by GpuSort when the gathered tensors
+    are on the device (nccl), by a stable numpy lexsort over the same
+    normalised keys when they are on the CPU (gloo). The result is, by
+    definition, the stable sort of the rank-ordered concatenation, cut to
+    `limit`. Returns (keys, payloads, nulls) as lists of tensors. With one
+    rank or no process group the input is returned as is. All ranks must
+    pass the same columns (a null mask on one rank = on every rank)."""
+    from . import executor as ex
+    key_cols, payload_cols = list(key_cols), list(payload_cols)
+    nk = len(key_cols)
+    nulls = [None] * nk if nulls is None else list(nulls)
+    flags = ex.sort_flags(nk, descending, nulls_first)
+    if not is_dist() or dist.get_world_size() == 1:
+        return key_cols, payload_cols, nulls
+    gk = [allgather_variable(k) for k in key_cols]
+    gp = [allgather_variable(p) for p in payload_cols]
+    gn = [None if m is None else allgather_variable(m) for m in nulls]
+    if gk[0].is_cuda:
+        node = ex.GpuSort(gk, [bool(f & 1) for f in flags],
+                          [bool(f & 2) for f in flags], gn, limit)
+        node.BeginCustomScan()
+        perm = node.ExecCustomScan()
+        node.EndCustomScan()
+
+        def take(t):
+            return ex.gather(t, perm)
+    else:
+        import numpy as np
+        cols = []   # np.lexsort: LAST entry is the primary key
+        for c in range(nk - 1, -1, -1):
+            nd, k = _sort_norm_host(gk[c].numpy(), flags[c],
+                                    None if gn[c] is None else gn[c].numpy())
+            cols += [k, nd]
+        order = np.lexsort(cols)
+        if limit > 0:
+            order = order[:limit]
+        perm = torch.from_numpy(order.astype(np.int64))
+
+        def take(t):
+            return t[perm]
+    return ([take(k) for k in gk], [take(p) for p in gp],
+            [None if m is None else take(m) for m in gn])
+
+
 def combine_var_state(a, b):
     """float8_combine (float.c:2725) on two [N, Sx, Sxx] transition states:
     the generalised Youngs-Cramer merge, in the reference's operation order

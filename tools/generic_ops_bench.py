@@ -6,6 +6,10 @@ distinct from the fused query pipelines.
   generic_ops_bench.py             agg + join shapes
   generic_ops_bench.py --agg-var   agg and agg_var at the same three shapes
                                    in one process (profiles/agg_var_ops.txt)
+  generic_ops_bench.py --sort [--out PATH]
+                                   otbx_sort_perm next to otbx_order_groups,
+                                   600 M-row sorts and LIMIT (writes
+                                   profiles/sort_ops.txt, or PATH)
 """
 import ctypes as C
 import os
@@ -192,8 +196,171 @@ def bench_round2_ops():
             C.c_void_p(npairs.data_ptr()), stream), n)
 
 
+COPY_CEILING = 6.29e12   # B/s, the measured copy ceiling (README)
+
+
+def _best_of_5(fn):
+    """warm-up, then 5 timed repetitions ending in a device synchronise;
+    returns (best, worst) seconds"""
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(5):
+        t0 = time.time()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.time() - t0)
+    return min(ts), max(ts)
+
+
+def _varying_bytes(col):
+    """radix passes otbx_sort_perm executes for this column: key bytes that
+    are not constant over the rows (constant ones are skipped on the
+    device). The normalisation maps each byte one-to-one, so the raw bit
+    pattern tells (no NaN / -0 in the benchmark data)."""
+    width = col.element_size()
+    raw = col.view({1: torch.uint8, 4: torch.int32, 8: torch.int64}[width])
+    n = 0
+    for b in range(width):
+        byte = (raw >> (8 * b)) & 0xff if width > 1 else raw
+        n += int(byte.min().item() != byte.max().item())
+    return n
+
+
+class _SortCall:
+    def __init__(self, keys, descending, limit=0):
+        self.node = ex.GpuSort(keys, descending=descending, limit=limit)
+        self.n, self.limit = len(keys[0]), limit
+        L = lib()
+        wsb = C.c_size_t(0)
+        L.otbx_sort_workspace_bytes(C.c_int64(self.n), C.c_int32(len(keys)),
+                                    C.c_int64(limit), C.byref(wsb))
+        self.wsb = wsb.value
+        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device="cuda")
+        cap = min(limit, self.n) if limit else self.n
+        self.perm = torch.empty(cap, dtype=torch.int64, device="cuda")
+        self.nout = torch.zeros(1, dtype=torch.int64, device="cuda")
+        self.spec = self.node.spec()
+        self.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def __call__(self):
+        call("otbx_sort_perm", C.byref(self.spec), C.c_int64(self.n),
+             C.c_int64(self.limit), C.c_void_p(self.ws.data_ptr()),
+             C.c_size_t(self.wsb), C.c_void_p(self.perm.data_ptr()),
+             C.c_void_p(self.nout.data_ptr()), self.stream)
+
+
+def _check_sorted(key, perm):
+    """sorted ascending, and equal keys keep row order (stable)"""
+    k = key[perm]
+    ok = bool((k[1:] >= k[:-1]).all().item())
+    tie = k[1:] == k[:-1]
+    return ok and bool((perm[1:][tie] > perm[:-1][tie]).all().item())
+
+
+def bench_sort(out_path):
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    say("# tools/generic_ops_bench.py --sort — best of 5 wall time after "
+        "torch.cuda.synchronize()")
+    say("# row-passes/s = n x executed radix passes / time; 24 B per row-pass "
+        "(8 B key + 4 B row id, read and written)")
+    g = torch.Generator(device="cuda").manual_seed(5)
+
+    # (a) Q3-shaped groups: (revenue DESC, o_orderdate ASC), both operators
+    n = 13_900_000
+    rev = (torch.rand(n, dtype=torch.float64, device="cuda", generator=g)
+           * 5e5 + 1.0)
+    date = torch.randint(0, 2400, (n,), dtype=torch.int32, device="cuda",
+                         generator=g)
+    rec = torch.zeros(n, 3, dtype=torch.int64, device="cuda")
+    rec[:, 0] = torch.arange(n, device="cuda")
+    rec[:, 1] = rev.view(torch.int64)
+    rec[:, 2] = date.to(torch.int64)          # o_shippriority = 0 (high half)
+    groups = rec.view(torch.uint8).reshape(-1)
+    L = lib()
+    wsb = C.c_size_t(0)
+    L.otbx_order_groups_workspace_bytes(C.c_int64(n), C.byref(wsb))
+    ws = torch.empty(wsb.value, dtype=torch.uint8, device="cuda")
+    out = torch.empty(n * 24, dtype=torch.uint8, device="cuda")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def old():
+        call("otbx_order_groups", C.c_void_p(groups.data_ptr()), C.c_int64(n),
+             C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()),
+             C.c_size_t(wsb.value), stream)
+
+    new = _SortCall([rev, date], [True, False])
+    ob, ow = _best_of_5(old)
+    nb, nw = _best_of_5(new)
+    ob2, ow2 = _best_of_5(old)                 # alternate: old, new, old
+    ob, ow = min(ob, ob2), max(ow, ow2)
+    passes = _varying_bytes(rev) + _varying_bytes(date)
+    old_rate, new_rate = n * 10 / ob, n * passes / nb
+    old_key = out.view(torch.int64).reshape(n, 3)[:, 0]
+    same = bool((old_key == new.perm).all().item())
+    say(f"(a) n={n:_} (f64 DESC, i32 ASC), same process")
+    say(f"    otbx_order_groups: best {ob*1e3:8.2f} ms  worst {ow*1e3:8.2f} ms"
+        f"  10 passes  {old_rate/1e9:6.2f} G row-passes/s "
+        f"(spread {(ow-ob)/ob*100:.1f} %)")
+    say(f"    otbx_sort_perm   : best {nb*1e3:8.2f} ms  worst {nw*1e3:8.2f} ms"
+        f"  {passes} passes executed of 12  {new_rate/1e9:6.2f} G row-passes/s"
+        f" (spread {(nw-nb)/nb*100:.1f} %)")
+    say(f"    row-passes/s ratio new/old: {new_rate/old_rate:.2f}; "
+        f"time ratio old/new: {ob/nb:.2f}; same row order: {same}")
+    del rec, groups, ws, out, new, rev, date, old_key
+    torch.cuda.empty_cache()
+
+    # (b) 600 M uniform i64, (d) the same with LIMIT; (c) 600 M i32
+    n = 600_000_000
+    k64 = torch.randint(-2**62, 2**62, (n,), dtype=torch.int64, device="cuda",
+                        generator=g)
+    full = _SortCall([k64], [False])
+    fb, fw = _best_of_5(full)
+    p = _varying_bytes(k64)
+    say(f"(b) n={n:_} one uniform i64 key: best {fb*1e3:8.2f} ms  worst "
+        f"{fw*1e3:8.2f} ms  {p} passes  {n*p/fb/1e9:6.2f} G row-passes/s  "
+        f"{n*p*24/fb/1e12:5.2f} TB/s per pass = "
+        f"{n*p*24/fb/COPY_CEILING*100:4.1f} % of the 6.29 TB/s copy ceiling; "
+        f"sorted+stable: {_check_sorted(k64, full.perm)}")
+    for limit in (10, 100_000):
+        lim = _SortCall([k64], [False], limit)
+        lb, lw = _best_of_5(lim)
+        agree = bool((lim.perm == full.perm[:limit]).all().item())
+        say(f"(d) n={n:_} i64 LIMIT {limit:_}: best {lb*1e3:8.2f} ms  worst "
+            f"{lw*1e3:8.2f} ms  ratio to (b): {lb/fb:.3f}; "
+            f"equals full-sort prefix: {agree}")
+        del lim
+    del full, k64
+    torch.cuda.empty_cache()
+    k32 = torch.randint(-2**31, 2**31 - 1, (n,), dtype=torch.int32,
+                        device="cuda", generator=g)
+    c = _SortCall([k32], [False])
+    cb, cw = _best_of_5(c)
+    p = _varying_bytes(k32)
+    say(f"(c) n={n:_} one uniform i32 key: best {cb*1e3:8.2f} ms  worst "
+        f"{cw*1e3:8.2f} ms  {p} passes  {n*p/cb/1e9:6.2f} G row-passes/s  "
+        f"{n*p*24/cb/1e12:5.2f} TB/s per pass = "
+        f"{n*p*24/cb/COPY_CEILING*100:4.1f} % of the 6.29 TB/s copy ceiling; "
+        f"sorted+stable: {_check_sorted(k32, c.perm)}")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
     ex.init_device(0)
+    if "--sort" in sys.argv:
+        repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        out_path = os.path.join(repo, "profiles", "sort_ops.txt")
+        if "--out" in sys.argv:
+            out_path = sys.argv[sys.argv.index("--out") + 1]
+        bench_sort(out_path)
+        sys.exit(0)
     if "--agg-var" in sys.argv:
         for groups in (4, 1_000_000, 100_000_000):
             t_agg = bench_agg(600_000_000, groups)
