@@ -38,6 +38,10 @@
  *   otbx_sort_perm         — the Sort node for any tuple shape: ExecSort
  *                            (executor/nodeSort.c:49) → tuplesort.c, with
  *                            the bounded top-N of a Limit above it
+ *   otbx_window            — the WindowAgg node over that sorted input:
+ *                            ExecWindowAgg (executor/nodeWindowAgg.c) with
+ *                            row_number / rank / dense_rank and count / sum
+ *                            over the default frame (windowfuncs.c:82-118)
  *   merge (Coordinator)    — NOT here: the shard merge (execFragment.c:3877)
  *                            is a collective over ranks, done by the host
  *                            layer with RCCL (torch.distributed) on the
@@ -552,6 +556,91 @@ otbx_status otbx_sort_workspace_bytes(int64_t n, int32_t nkeys, int64_t limit,
 otbx_status otbx_sort_perm(const otbx_sortspec *spec, int64_t n, int64_t limit,
                            void *ws_dev, size_t ws_bytes,
                            int64_t *perm_dev, int64_t *nout_dev, void *stream);
+
+/* ---- GPU WindowAgg: ranking and running aggregates over sorted input ----
+ * The ExecWindowAgg analog (executor/nodeWindowAgg.c; window functions in
+ * utils/adt/windowfuncs.c) for ONE window specification
+ *     OVER (PARTITION BY key[0..npart) ORDER BY key[npart..nkeys))
+ * with the reference's default frame. It is the pass over the permutation
+ * otbx_sort_perm produced for exactly these keys.
+ *
+ * INPUTS
+ *   - spec lists the key columns the input is sorted by: the first npart
+ *     keys are the PARTITION BY columns, the rest the ORDER BY columns.
+ *     spec->nkeys may be 0..8 and 0 <= npart <= nkeys. With nkeys == 0 all
+ *     rows form one partition of peers.
+ *   - perm_dev is what otbx_sort_perm(spec, n, limit = 0) returned: row
+ *     perm[j] is the j-th row in sorted order. NULL means identity (the
+ *     columns are already in order). The caller guarantees it is a sorted
+ *     permutation of [0, n); this is not checked (an entry outside [0, n) is
+ *     clamped, so it cannot address outside the columns).
+ *   - vals_dev / val_null_dev (byte per row, nonzero = NULL; may be NULL)
+ *     are indexed by INPUT row and read through perm.
+ *   - every output is indexed by SORTED POSITION j — WindowAgg emits rows in
+ *     sorted order. Each out-> pointer is a device array of n entries, or
+ *     NULL = not wanted: nothing is loaded or stored for it, and a call that
+ *     asks for ranking outputs only never touches vals_dev.
+ *
+ * EQUALITY (are_peers, nodeWindowAgg.c:2960, over ApplySortComparator)
+ *   Two adjacent rows are in the same partition iff they compare EQUAL on
+ *   every partition key, and are peers iff they are also equal on every
+ *   order key. Equal means what otbx_sort_perm means — NULL equals NULL,
+ *   every NaN equals every NaN, -0.0 == +0.0, the value stored under a NULL
+ *   is ignored — because the test is made on the sort's own normalised key
+ *   (null bit + normalised bits).
+ *
+ * FRAME: RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW (row_is_in_frame,
+ *   nodeWindowAgg.c:1472-1505): from the partition's first row through the
+ *   LAST PEER of the current row. All peers therefore receive identical
+ *   count_star / count_v / sum_v / sum_isnull, and with npart == nkeys the
+ *   whole partition is the frame.
+ *
+ * OUTPUTS
+ *   row_number = j - partition_start + 1          (window_row_number :82)
+ *   rank       = peer_group_start - partition_start + 1  (window_rank :98)
+ *   dense_rank = peer groups up to and including the current one    (:118)
+ *   part_rows  = rows in the partition (WinGetPartitionRowCount)
+ *   count_star = rows in the frame; count_v = its non-NULL values
+ *   sum_v      = their float8pl sum; NULL (sum_isnull = 1, value 0.0) when
+ *                the frame holds no non-NULL value.
+ *
+ * NUMERICS OF sum_v: the scan is SEGMENTED — a partition's sums are computed
+ *   from that partition's values only, so an Inf, NaN or 1e300 in one
+ *   partition never reaches another, and nothing is obtained as a
+ *   difference of prefix sums. Inside a partition the association order
+ *   differs from the reference's left-to-right float8pl (tiled tree); the
+ *   result is within the standard recursive-summation bound
+ *   m*u*sum|x| / (1 - m*u), u = 2^-53, and exact wherever every order is
+ *   (integer-valued doubles). Overflow of finite inputs is not detected
+ *   (same clause as otbx_agg_i64_var).
+ *
+ * Stream-ordered, no host synchronisation and no device-to-host channel.
+ * Checked before any HIP call, each returning OTBX_ERR_INVALID: spec or out
+ * NULL; nkeys outside 0..8; npart outside 0..nkeys; a type code outside
+ * 0..3 or flags outside bits 0-1; n < 0 or n > INT32_MAX; a NULL key column
+ * with n > 0; no output requested; sum_v without sum_isnull or the reverse;
+ * sum_v or count_v requested with vals_dev == NULL; ws_bytes below
+ * otbx_window_workspace_bytes(n), or ws_dev not 16-byte aligned. n == 0 is
+ * valid and writes nothing.
+ * otbx_window_workspace_bytes is pure host code and monotone in n. Nothing
+ * is cached by this entry point (otbx_finish has nothing to release). */
+typedef struct {            /* each pointer: device array of n entries, or NULL = not wanted */
+    int64_t *row_number;    /* window_row_number, windowfuncs.c:82  */
+    int64_t *rank;          /* window_rank        :98               */
+    int64_t *dense_rank;    /* window_dense_rank  :118              */
+    int64_t *count_star;    /* count(*) over the frame              */
+    int64_t *count_v;       /* count(v) over the frame              */
+    double  *sum_v;         /* sum(v)  over the frame (float8pl)    */
+    uint8_t *sum_isnull;    /* 1 where the frame holds no non-NULL v */
+    int64_t *part_rows;     /* rows in the partition (WinGetPartitionRowCount) */
+} otbx_window_out;
+
+otbx_status otbx_window_workspace_bytes(int64_t n, size_t *bytes);
+otbx_status otbx_window(const otbx_sortspec *spec, int32_t npart,
+                        const int64_t *perm_dev, int64_t n,
+                        const double *vals_dev, const uint8_t *val_null_dev,
+                        void *ws_dev, size_t ws_bytes,
+                        const otbx_window_out *out, void *stream);
 
 /* ---- repartition exchange ----
  * The GPU half of the reference's "Distribute results by H: col" exchange

@@ -76,6 +76,15 @@ class SortSpecDev(C.Structure):
     _fields_ = [("nkeys", C.c_int32), ("key", SortKeyDev * 8)]
 
 
+class WindowOutDev(C.Structure):
+    """otbx_window_out: one device array of n entries per requested window
+    function, None = not wanted."""
+    _fields_ = [("row_number", C.c_void_p), ("rank", C.c_void_p),
+                ("dense_rank", C.c_void_p), ("count_star", C.c_void_p),
+                ("count_v", C.c_void_p), ("sum_v", C.c_void_p),
+                ("sum_isnull", C.c_void_p), ("part_rows", C.c_void_p)]
+
+
 class PartDev(C.Structure):
     _fields_ = [
         ("n", C.c_int64),
@@ -111,6 +120,7 @@ def lib():
         _lib.otbx_q3_workspace_bytes.argtypes = [i64, i64, i64, szp]
         _lib.otbx_q9_workspace_bytes.argtypes = [i64, i64, i64, u32, szp]
         _lib.otbx_sort_workspace_bytes.argtypes = [i64, C.c_int32, i64, szp]
+        _lib.otbx_window_workspace_bytes.argtypes = [i64, szp]
     return _lib
 
 
@@ -145,4 +155,5 @@ EXPORTED_SYMBOLS = [
     "otbx_agg_i64n_workspace_bytes", "otbx_agg_i64n",
     "otbx_join_i64n_workspace_bytes", "otbx_join_i64n",
     "otbx_sort_workspace_bytes", "otbx_sort_perm",
+    "otbx_window_workspace_bytes", "otbx_window",
 ]

@@ -17,7 +17,8 @@ import math
 import torch
 
 from ._lib import (CustomerDev, KeysetDev, LineitemDev, OrdersDev,
-                   OtbxError, PartDev, SortSpecDev, call, check, lib)
+                   OtbxError, PartDev, SortSpecDev, WindowOutDev, call, check,
+                   lib)
 
 Q1_SLOT_ORDER = [(b"A", b"F"), (b"A", b"O"), (b"N", b"F"),
                  (b"N", b"O"), (b"R", b"F"), (b"R", b"O")]
@@ -644,6 +645,162 @@ class GpuSort(CustomScanState):
         if self.sort_ms is None:
             return None
         return {"sort": self.sort_ms}
+
+
+WINDOW_FUNCS = ("row_number", "rank", "dense_rank", "count_star", "count_v",
+                "sum_v", "part_rows")
+_WINDOW_DTYPE = {"sum_v": torch.float64, "sum_isnull": torch.uint8}
+
+
+class GpuWindowAgg(CustomScanState):
+    """The WindowAgg node (nodeWindowAgg.c) for one window specification
+    OVER (PARTITION BY partition_by ORDER BY order_by) with the default
+    frame: row_number / rank / dense_rank / part_rows and count(*) /
+    count(v) / sum(v) over RANGE UNBOUNDED PRECEDING .. CURRENT ROW.
+    Partition keys sort ASC with the SQL-default NULL placement; order keys
+    take descending / nulls_first as GpuSort does (sort_flags). Runs GpuSort
+    on the combined key list (skipped with zero keys: perm = NULL), then
+    otbx_window. Yields ONE tuple: a dict of device tensors, indexed by
+    sorted position, for the requested funcs (WINDOW_FUNCS; "sum_v" also
+    yields "sum_isnull") plus "perm". Contract in include/otbx.h
+    (otbx_window); finalize percent_rank / cume_dist with the functions
+    below."""
+
+    def __init__(self, partition_by, order_by, descending=None,
+                 nulls_first=None, part_nulls=None, order_nulls=None,
+                 vals=None, val_null=None, funcs=None, n=None):
+        super().__init__()
+        self.partition_by, self.order_by = list(partition_by), list(order_by)
+        self.keys = self.partition_by + self.order_by
+        npart, nord = len(self.partition_by), len(self.order_by)
+        if npart + nord > 8:
+            raise OtbxError(3, "window: at most 8 keys")
+        pn = [None] * npart if part_nulls is None else list(part_nulls)
+        on = [None] * nord if order_nulls is None else list(order_nulls)
+        if len(pn) != npart or len(on) != nord:
+            raise OtbxError(3, "window: one nulls entry per key")
+        self.nulls = pn + on
+        self.flags = sort_flags(npart) + \
+            sort_flags(nord, descending, nulls_first)
+        self.vals, self.val_null = vals, val_null
+        if funcs is None:
+            funcs = WINDOW_FUNCS if vals is not None else \
+                ("row_number", "rank", "dense_rank", "count_star", "part_rows")
+        self.funcs = tuple(funcs)
+        for f in self.funcs:
+            if f not in WINDOW_FUNCS:
+                raise OtbxError(3, f"window: unknown function {f}")
+        if not self.funcs:
+            raise OtbxError(3, "window: no function requested")
+        if vals is None and ("sum_v" in self.funcs or "count_v" in self.funcs):
+            raise OtbxError(3, "window: sum_v / count_v need vals")
+        for k in self.keys:
+            if k.dtype not in _SORT_TYPE:
+                raise OtbxError(3, f"window: unsupported key dtype {k.dtype}")
+        if n is None:
+            if self.keys:
+                n = len(self.keys[0])
+            elif vals is not None:
+                n = len(vals)
+            else:
+                raise OtbxError(3, "window: no keys and no vals — pass n")
+        self.n = int(n)
+        for k in self.keys:
+            if len(k) != self.n:
+                raise OtbxError(3, "window: key columns differ in length")
+        self.perm = None
+        self.sort_ms = None
+        self.window_ms = None
+
+    def _run(self):
+        L = lib()
+        n = self.n
+        self.sort_ms = 0.0
+        perm = None
+        if self.keys:
+            srt = GpuSort(self.keys, nulls=self.nulls)
+            srt.flags = list(self.flags)
+            srt.BeginCustomScan()
+            perm = srt.ExecCustomScan()
+            srt.EndCustomScan()
+            self.sort_ms = srt.sort_ms
+            sp = srt.spec()
+        else:
+            sp = SortSpecDev()
+            sp.nkeys = 0
+        ws_bytes = C.c_size_t(0)
+        check(L.otbx_window_workspace_bytes(C.c_int64(n), C.byref(ws_bytes)),
+              "otbx_window_workspace_bytes")
+        ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8,
+                         device="cuda")
+        names = list(self.funcs)
+        if "sum_v" in names:
+            names.append("sum_isnull")
+        res = {f: torch.empty(max(n, 1),
+                              dtype=_WINDOW_DTYPE.get(f, torch.int64),
+                              device="cuda") for f in names}
+        out = WindowOutDev()
+        for f, t in res.items():
+            setattr(out, f, t.data_ptr())
+
+        def vp(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+
+        # an empty tensor has no address: with no rows, hand the argument
+        # check a placeholder so that "vals given" stays visible to it
+        vals = self.vals
+        if vals is not None and n == 0:
+            vals = torch.zeros(1, dtype=torch.float64, device="cuda")
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        call("otbx_window", C.byref(sp), C.c_int32(len(self.partition_by)),
+             vp(perm), C.c_int64(n), vp(vals), vp(self.val_null),
+             C.c_void_p(ws.data_ptr()), C.c_size_t(ws_bytes.value),
+             C.byref(out), _stream())
+        ev1.record()
+        ev1.synchronize()
+        self.window_ms = ev0.elapsed_time(ev1)
+        res = {f: t[:n] for f, t in res.items()}
+        self.perm = perm if perm is not None else \
+            torch.arange(n, dtype=torch.int64, device="cuda")
+        res["perm"] = self.perm
+        return [res]
+
+    def gather(self, col):
+        """col in sorted order (runs the node if it has not run)."""
+        if self.perm is None:
+            self._run()
+        return gather(col, self.perm)
+
+    def explain(self):
+        if self.window_ms is None:
+            return None
+        return {"sort": self.sort_ms, "window": self.window_ms}
+
+
+# window-function finalizers over the node's integer outputs (scalars or
+# numpy arrays in, float or float64 array out)
+
+def percent_rank(rank, part_rows):
+    """window_percent_rank (windowfuncs.c:140): (rank - 1) / (NP - 1), and 0
+    when the partition has a single row."""
+    import numpy as np
+    r = np.asarray(rank, dtype=np.float64)
+    tp = np.asarray(part_rows, dtype=np.float64)
+    out = np.where(tp <= 1.0, 0.0, (r - 1.0) / np.where(tp <= 1.0, 1.0,
+                                                         tp - 1.0))
+    return float(out) if out.ndim == 0 else out
+
+
+def cume_dist(count_star, part_rows):
+    """window_cume_dist (windowfuncs.c:189): NP / partition rows, where NP
+    (rows preceding or peer with the current row) is exactly the
+    default-frame count(*)."""
+    import numpy as np
+    out = np.asarray(count_star, dtype=np.float64) / \
+        np.asarray(part_rows, dtype=np.float64)
+    return float(out) if out.ndim == 0 else out
 
 
 class GpuHashAgg(CustomScanState):

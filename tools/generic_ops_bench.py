@@ -10,6 +10,11 @@ distinct from the fused query pipelines.
                                    otbx_sort_perm next to otbx_order_groups,
                                    600 M-row sorts and LIMIT (writes
                                    profiles/sort_ops.txt, or PATH)
+  generic_ops_bench.py --window [--out PATH]
+                                   otbx_window at 600 M rows, timed apart
+                                   from its sort, next to a plain-torch
+                                   composition of the ranking functions
+                                   (writes profiles/window_ops.txt, or PATH)
 """
 import ctypes as C
 import os
@@ -20,7 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from opentenbase_amd import executor as ex  # noqa: E402
-from opentenbase_amd._lib import call, lib  # noqa: E402
+from opentenbase_amd._lib import WindowOutDev, call, lib  # noqa: E402
 
 
 def bench_agg(n, ngroups):
@@ -351,9 +356,162 @@ def bench_sort(out_path):
     with open(out_path, "w") as f:
         f.write("\n".join(lines) + "\n")
 
+_WIN_RANKING = ("row_number", "rank", "dense_rank")
+_WIN_ALL = ("row_number", "rank", "dense_rank", "count_star", "count_v",
+            "sum_v", "part_rows")
+
+
+class _WindowCall:
+    """otbx_window on an already sorted permutation, buffers allocated once"""
+
+    def __init__(self, srt, npart, vals, funcs):
+        self.n, self.npart, self.vals = srt.n, npart, vals
+        self.spec, self.perm, self.stream = srt.spec, srt.perm, srt.stream
+        wsb = C.c_size_t(0)
+        lib().otbx_window_workspace_bytes(C.c_int64(self.n), C.byref(wsb))
+        self.wsb = wsb.value
+        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device="cuda")
+        self.res, self.out = {}, WindowOutDev()
+        names = list(funcs) + (["sum_isnull"] if "sum_v" in funcs else [])
+        for f in names:
+            dt = {"sum_v": torch.float64, "sum_isnull": torch.uint8}.get(
+                f, torch.int64)
+            self.res[f] = torch.empty(self.n, dtype=dt, device="cuda")
+            setattr(self.out, f, self.res[f].data_ptr())
+
+    def __call__(self):
+        v = self.vals
+        call("otbx_window", C.byref(self.spec), C.c_int32(self.npart),
+             C.c_void_p(self.perm.data_ptr()) if self.perm is not None
+             else None, C.c_int64(self.n),
+             C.c_void_p(v.data_ptr()) if v is not None else None, None,
+             C.c_void_p(self.ws.data_ptr()), C.c_size_t(self.wsb),
+             C.byref(self.out), self.stream)
+
+
+def _window_bytes_per_row(key_bytes, funcs):
+    """algorithmic bytes of one otbx_window call per row: perm and keys
+    gathered once, values gathered once, every requested output written
+    once, flag / scan workspace written and read back"""
+    b = 8 + key_bytes + 2                      # perm, keys, flag byte w + r
+    b += 8 * sum(f != "sum_v" for f in funcs)
+    if "sum_v" in funcs or "count_v" in funcs:
+        b += 8 + 8                             # running count, frame end: w + r
+    if "sum_v" in funcs:
+        b += 8 + 4 * 8 + 8 + 1    # vals; value w/r, running sum w/r; sum, null
+    return b
+
+
+def _torch_ranking(pk, ok, perm):
+    """what a caller would write without the operator: the ranking functions
+    from boundary masks, cummax and cumsum on the same sorted data"""
+    n = len(perm)
+    sp, so = pk[perm], ok[perm]
+    ps = torch.ones(n, dtype=torch.bool, device="cuda")
+    ps[1:] = sp[1:] != sp[:-1]
+    gs = ps.clone()
+    gs[1:] |= so[1:] != so[:-1]
+    del sp, so
+    pos = torch.arange(n, dtype=torch.int64, device="cuda")
+    zero = torch.zeros((), dtype=torch.int64, device="cuda")
+    pstart = torch.cummax(torch.where(ps, pos, zero), 0).values
+    gstart = torch.cummax(torch.where(gs, pos, zero), 0).values
+    cg = torch.cumsum(gs, 0)
+    return {"row_number": pos - pstart + 1, "rank": gstart - pstart + 1,
+            "dense_rank": cg - cg[pstart] + 1}
+
+
+def bench_window(out_path):
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    say("# tools/generic_ops_bench.py --window — best / worst of 5 wall time "
+        "after torch.cuda.synchronize(), keys staged")
+    say("# PARTITION BY an i64 key ORDER BY an i32 key (100 distinct values); "
+        "the sort and otbx_window are timed apart")
+    g = torch.Generator(device="cuda").manual_seed(9)
+    n = 600_000_000
+    ok = torch.randint(0, 100, (n,), dtype=torch.int32, device="cuda",
+                       generator=g)
+    vals = torch.randint(-1000, 1001, (n,), dtype=torch.int64, device="cuda",
+                         generator=g).to(torch.float64)
+    pk_many = torch.randint(0, 1_000_000, (n,), dtype=torch.int64,
+                            device="cuda", generator=g)
+    pk_one = torch.zeros(n, dtype=torch.int64, device="cuda")
+    cases = [("a", "ranking only, ~1 M partitions", pk_many, None,
+              _WIN_RANKING),
+             ("b", "all outputs, ~1 M partitions", pk_many, vals, _WIN_ALL),
+             ("c", "all outputs, one partition", pk_one, vals, _WIN_ALL)]
+    srt, srt_pk = None, None
+    for tag, what, pk, v, funcs in cases:
+        if srt_pk is not pk:
+            del srt
+            torch.cuda.empty_cache()
+            srt = _SortCall([pk, ok], [False, False])
+            sb, sw = _best_of_5(srt)
+            srt_pk = pk
+        win = _WindowCall(srt, 1, v, funcs)
+        wb, ww = _best_of_5(win)
+        bpr = _window_bytes_per_row(12, funcs)
+        tbs = n * bpr / wb / 1e12
+        say(f"({tag}) n={n:_} {what}: sort best {sb*1e3:8.2f} ms  worst "
+            f"{sw*1e3:8.2f} ms | otbx_window best {wb*1e3:8.2f} ms  worst "
+            f"{ww*1e3:8.2f} ms (spread {(ww-wb)/wb*100:.1f} %)  {bpr} B/row "
+            f"algorithmic = {n*bpr/1e9:.1f} GB  {tbs:5.2f} TB/s = "
+            f"{tbs*1e12/COPY_CEILING*100:4.1f} % of the 6.29 TB/s copy ceiling")
+        if tag == "a":
+            tb, tw = _best_of_5(lambda: _torch_ranking(pk, ok, srt.perm))
+            ref = _torch_ranking(pk, ok, srt.perm)
+            same = all(bool(torch.equal(ref[f], win.res[f])) for f in ref)
+            parts = int((win.res["row_number"] == 1).sum().item())
+            say(f"    plain torch (mask, cummax, cumsum) on the same sorted "
+                f"data: best {tb*1e3:8.2f} ms  worst {tw*1e3:8.2f} ms; "
+                f"torch / otbx_window time ratio: {tb/wb:.2f}; same values: "
+                f"{same}; partitions: {parts:_}")
+            del ref, win
+            # the same call on pre-gathered keys with perm = NULL: what is
+            # left when the loads through perm are sequential instead
+            class _Sorted:
+                pass
+            pre = _Sorted()
+            pre.keys = [pk[srt.perm], ok[srt.perm]]
+            pre.n, pre.perm, pre.stream = n, None, srt.stream
+            pre.spec = ex.GpuSort(pre.keys).spec()
+            win = _WindowCall(pre, 1, None, funcs)
+            ib, iw = _best_of_5(win)
+            ibpr = bpr - 8
+            say(f"    same call, keys pre-gathered, perm = NULL: best "
+                f"{ib*1e3:8.2f} ms  worst {iw*1e3:8.2f} ms  {ibpr} B/row = "
+                f"{n*ibpr/ib/1e12:5.2f} TB/s = "
+                f"{n*ibpr/ib/COPY_CEILING*100:4.1f} % of the ceiling; the "
+                f"gather through perm costs {(wb-ib)*1e3:.2f} ms of (a)")
+            del pre
+        else:
+            tot = float(v.sum().item()) if tag == "c" else None
+            last = float(win.res["sum_v"][-1].item())
+            say(f"    count_v[-1]={int(win.res['count_v'][-1].item()):_} "
+                f"part_rows[-1]={int(win.res['part_rows'][-1].item()):_} "
+                f"sum_v[-1]={last}" +
+                (f" (column total {tot})" if tot is not None else ""))
+        del win
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
 
 if __name__ == "__main__":
     ex.init_device(0)
+    if "--window" in sys.argv:
+        repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        out_path = os.path.join(repo, "profiles", "window_ops.txt")
+        if "--out" in sys.argv:
+            out_path = sys.argv[sys.argv.index("--out") + 1]
+        bench_window(out_path)
+        sys.exit(0)
     if "--sort" in sys.argv:
         repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         out_path = os.path.join(repo, "profiles", "sort_ops.txt")
