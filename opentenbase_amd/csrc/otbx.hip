@@ -25,29 +25,13 @@
  *                   keys equal (execGrouping.c:520), NULL join keys never
  *                   match (nodeHash.c:2026)
  */
-#include <hip/hip_runtime.h>
-#include <limits.h>
-#include <stdio.h>
 #include <stdlib.h>  /* getenv, atoll */
 #include <string.h>
 
-#include "../../include/otbx.h"
+#include "otbx_common.h"
 #include "../../oracle/otbx_gen.h"   /* shared deterministic datagen */
 
 #define OTBX_VERSION_STR "otbx 0.1 gfx950"
-
-/* wave width is 64 on CDNA4 — hard-coded per the HIP guide */
-#define WAVE 64
-
-#define HIP_CHECK(x)                                                     \
-    do {                                                                 \
-        hipError_t err_ = (x);                                           \
-        if (err_ != hipSuccess) {                                        \
-            fprintf(stderr, "otbx: HIP error %s at %s:%d\n",             \
-                    hipGetErrorString(err_), __FILE__, __LINE__);        \
-            return OTBX_ERR_HIP;                                         \
-        }                                                                \
-    } while (0)
 
 /* Lazily-cached per-process scratch (the function-local statics below):
  * every allocation registers its slot here so otbx_finish can release it
@@ -63,12 +47,22 @@ static int g_nscr = 0;
 static hipError_t otbx_scr_alloc(void **slot, size_t bytes, int host)
 {
     hipError_t e = host ? hipHostMalloc(slot, bytes) : hipMalloc(slot, bytes);
-    if (e == hipSuccess && g_nscr < OTBX_SCRATCH_MAX) {
-        g_scr_slot[g_nscr] = slot;
-        g_scr_host[g_nscr] = (unsigned char)host;
-        g_nscr++;
+    if (e != hipSuccess)
+        return e;
+    if (g_nscr == OTBX_SCRATCH_MAX) {
+        /* an unregistered pointer would outlive otbx_finish and be reused on
+         * another device: refuse it instead */
+        if (host)
+            (void)hipHostFree(*slot);
+        else
+            (void)hipFree(*slot);
+        *slot = nullptr;
+        return hipErrorOutOfMemory;
     }
-    return e;
+    g_scr_slot[g_nscr] = slot;
+    g_scr_host[g_nscr] = (unsigned char)host;
+    g_nscr++;
+    return hipSuccess;
 }
 
 #define SCR_ALLOC_DEV(p, bytes) \
@@ -213,14 +207,6 @@ __global__ void k_gen_customer(otbx_customer_dev t, uint64_t seed,
         t.c_custkey[l] = otbx_cust_custkey(i);
         t.c_mktsegment[l] = otbx_cust_mktsegment(seed, i);
     }
-}
-
-static inline int grid_for(int64_t work, int block)
-{
-    int64_t g = (work + block - 1) / block;
-    if (g > 2048) g = 2048;   /* 256 CUs × 8 blocks; grid-stride the rest */
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 extern "C" {
@@ -752,37 +738,20 @@ struct agg_lds_slot {
     double sum;
 };
 
-__device__ __forceinline__ void d_agg_global_update(agg_slot *tab, int64_t mask,
-                                                    int64_t k,
-                                                    unsigned long long cs,
-                                                    unsigned long long cv,
-                                                    double sum)
-{
-    int64_t s = (int64_t)(d_hash_i64(k) & (uint64_t)mask);
-    for (;;) {
-        long long old = atomicCAS((unsigned long long *)&tab[s].key,
-                                  (unsigned long long)AGG_EMPTY,
-                                  (unsigned long long)k);
-        if (old == AGG_EMPTY || old == k) break;
-        s = (s + 1) & mask; /* simplehash linear probe */
-    }
-    atomicAdd(&tab[s].count_star, cs);
-    if (cv) {
-        atomicAdd(&tab[s].count_v, cv);
-        atomicAdd(&tab[s].sum_v, sum);
-    }
-}
+#define AGG_GLOBAL_PROBE_BOUND 256
 
-/* bounded variant for the small-table first attempt: gives up after
- * maxprobe steps (table effectively full → the sample-based sizing was
- * wrong) and reports failure instead of spinning */
+/* merge (cs, cv, sum) into key k's global slot (simplehash linear probe).
+ * BOUNDED is the small-table first attempt: it gives up after
+ * AGG_GLOBAL_PROBE_BOUND steps (table effectively full → the sample-based
+ * sizing was wrong) and returns false instead of spinning. */
+template <bool BOUNDED = false>
 __device__ __forceinline__ bool
-d_agg_global_update_b(agg_slot *tab, int64_t mask, int64_t k,
-                      unsigned long long cs, unsigned long long cv,
-                      double sum, int maxprobe)
+d_agg_global_update(agg_slot *tab, int64_t mask, int64_t k,
+                    unsigned long long cs, unsigned long long cv, double sum)
 {
     int64_t s = (int64_t)(d_hash_i64(k) & (uint64_t)mask);
-    for (int t = 0; t < maxprobe; t++) {
+    /* t counts only in the bounded form (t += 0 otherwise: no overflow) */
+    for (int t = 0; !BOUNDED || t < AGG_GLOBAL_PROBE_BOUND; t += BOUNDED) {
         long long old = atomicCAS((unsigned long long *)&tab[s].key,
                                   (unsigned long long)AGG_EMPTY,
                                   (unsigned long long)k);
@@ -799,21 +768,17 @@ d_agg_global_update_b(agg_slot *tab, int64_t mask, int64_t k,
     return false;
 }
 
-/* small-table build attempt: k_agg_build with bounded global probes + an
- * abort flag. When the estimator-sized table overflows (rare-key tail the
- * sample missed), the whole call is redone against the full-size table. */
-__global__ void k_agg_build_bounded(const int64_t *__restrict__ keys,
-                                    const uint8_t *__restrict__ knull,
-                                    const double *__restrict__ vals,
-                                    const uint8_t *__restrict__ vnull,
-                                    int64_t n, agg_slot *tab, int64_t cap,
-                                    agg_slot *nullgrp, unsigned int *abort);
-
+/* BOUNDED = the estimator-sized build attempt: bounded global probes + an
+ * abort flag. When that table overflows (rare-key tail the sample missed),
+ * the whole call is redone against the full-size table (BOUNDED = false,
+ * abort unused). */
+template <bool BOUNDED>
 __global__ void k_agg_build(const int64_t *__restrict__ keys,
                             const uint8_t *__restrict__ knull,
                             const double *__restrict__ vals,
                             const uint8_t *__restrict__ vnull, int64_t n,
-                            agg_slot *tab, int64_t cap, agg_slot *nullgrp)
+                            agg_slot *tab, int64_t cap, agg_slot *nullgrp,
+                            unsigned int *abort)
 {
     __shared__ agg_lds_slot ltab[AGG_LDS_SLOTS];
     for (int s = threadIdx.x; s < AGG_LDS_SLOTS; s += blockDim.x) {
@@ -825,8 +790,9 @@ __global__ void k_agg_build(const int64_t *__restrict__ keys,
     __syncthreads();
     int64_t mask = cap - 1;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += stride) {
+    bool dead = false;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         i < n && !dead; i += stride) {
         bool kn = knull && knull[i];
         bool vn = vnull && vnull[i];
         double v = vn ? 0.0 : vals[i];
@@ -859,83 +825,21 @@ __global__ void k_agg_build(const int64_t *__restrict__ keys,
             }
             s = (s + 1) & (AGG_LDS_SLOTS - 1);
         }
-        if (!placed) /* LDS window full: spill straight to the global table */
-            d_agg_global_update(tab, mask, k, 1ull, vn ? 0ull : 1ull, v);
-    }
-    __syncthreads();
-    /* flush LDS partials into the global table */
-    for (int s = threadIdx.x; s < AGG_LDS_SLOTS; s += blockDim.x) {
-        if (ltab[s].key != AGG_EMPTY)
-            d_agg_global_update(tab, mask, ltab[s].key,
-                                (unsigned long long)ltab[s].cs,
-                                (unsigned long long)ltab[s].cv, ltab[s].sum);
-    }
-}
-
-__global__ void k_agg_build_bounded(const int64_t *__restrict__ keys,
-                                    const uint8_t *__restrict__ knull,
-                                    const double *__restrict__ vals,
-                                    const uint8_t *__restrict__ vnull,
-                                    int64_t n, agg_slot *tab, int64_t cap,
-                                    agg_slot *nullgrp, unsigned int *abort)
-{
-    __shared__ agg_lds_slot ltab[AGG_LDS_SLOTS];
-    for (int s = threadIdx.x; s < AGG_LDS_SLOTS; s += blockDim.x) {
-        ltab[s].key = AGG_EMPTY;
-        ltab[s].cs = 0;
-        ltab[s].cv = 0;
-        ltab[s].sum = 0.0;
-    }
-    __syncthreads();
-    int64_t mask = cap - 1;
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    bool dead = false;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-         i < n && !dead; i += stride) {
-        bool kn = knull && knull[i];
-        bool vn = vnull && vnull[i];
-        double v = vn ? 0.0 : vals[i];
-        if (kn || keys[i] == AGG_EMPTY) {
-            agg_slot *e = kn ? nullgrp : nullgrp + 1;
-            atomicAdd(&e->count_star, 1ull);
-            if (!vn) {
-                atomicAdd(&e->count_v, 1ull);
-                atomicAdd(&e->sum_v, v);
-            }
-            continue;
-        }
-        int64_t k = keys[i];
-        int64_t s = (int64_t)(d_hash_i64(k) & (uint64_t)(AGG_LDS_SLOTS - 1));
-        bool placed = false;
-        for (int t = 0; t < AGG_LDS_PROBES; t++) {
-            long long old = atomicCAS((unsigned long long *)&ltab[s].key,
-                                      (unsigned long long)AGG_EMPTY,
-                                      (unsigned long long)k);
-            if (old == AGG_EMPTY || old == k) {
-                atomicAdd(&ltab[s].cs, 1u);
-                if (!vn) {
-                    atomicAdd(&ltab[s].cv, 1u);
-                    atomicAdd(&ltab[s].sum, v);
-                }
-                placed = true;
-                break;
-            }
-            s = (s + 1) & (AGG_LDS_SLOTS - 1);
-        }
-        if (!placed &&
-            !d_agg_global_update_b(tab, mask, k, 1ull, vn ? 0ull : 1ull, v,
-                                   256)) {
+        /* LDS window full: spill straight to the global table */
+        if (!placed && !d_agg_global_update<BOUNDED>(tab, mask, k, 1ull,
+                                                     vn ? 0ull : 1ull, v)) {
             atomicAdd(abort, 1u); /* undersized: caller redoes at full cap */
             dead = true;
         }
     }
     __syncthreads();
+    /* flush LDS partials into the global table */
     for (int s = threadIdx.x; s < AGG_LDS_SLOTS; s += blockDim.x) {
         if (ltab[s].key != AGG_EMPTY &&
-            !d_agg_global_update_b(tab, mask, ltab[s].key,
-                                   (unsigned long long)ltab[s].cs,
-                                   (unsigned long long)ltab[s].cv,
-                                   ltab[s].sum, 256))
+            !d_agg_global_update<BOUNDED>(tab, mask, ltab[s].key,
+                                          (unsigned long long)ltab[s].cs,
+                                          (unsigned long long)ltab[s].cv,
+                                          ltab[s].sum))
             atomicAdd(abort, 1u);
     }
 }
@@ -944,55 +848,17 @@ __global__ void k_agg_compact(const agg_slot *tab, int64_t cap,
                               const agg_slot *nullgrp,
                               otbx_agg_group *out, int64_t *ngroups)
 {
-    /* block-aggregated two-phase emission: ONE global reservation per block
-     * (a per-wave wave_append over a 1-billion-slot table made ~16 M
-     * global-counter reservations — measured 201 ms of a 339 ms call at
-     * cap 2^30; this form costs one extra pass over the block's range). */
-    __shared__ unsigned long long lbase;
-    __shared__ unsigned int lcnt, ltot;
-    if (threadIdx.x == 0) lcnt = 0;
-    __syncthreads();
-    int64_t per_block = (cap + gridDim.x - 1) / gridDim.x;
-    int64_t lo = blockIdx.x * per_block;
-    int64_t hi = lo + per_block < cap ? lo + per_block : cap;
-    int lane = (int)(threadIdx.x % WAVE);
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        unsigned long long mask = __ballot(tab[i].key != AGG_EMPTY);
-        if (lane == 0 && mask)
-            atomicAdd(&lcnt, (unsigned int)__popcll(mask));
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ltot = lcnt;
-        lbase = lcnt ? (unsigned long long)atomicAdd(
-                           (unsigned long long *)ngroups,
-                           (unsigned long long)lcnt)
-                     : 0;
-        lcnt = 0;
-    }
-    __syncthreads();
-    if (ltot == 0) goto specials; /* low-cardinality tables: most blocks
-                                   * scan an all-empty range — skip pass 2 */
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        bool used = tab[i].key != AGG_EMPTY;
-        unsigned long long mask = __ballot(used);
-        if (!mask) continue;
-        unsigned int wbase = 0;
-        if (lane == 0)
-            wbase = atomicAdd(&lcnt, (unsigned int)__popcll(mask));
-        wbase = (unsigned int)__shfl((int)wbase, 0, WAVE);
-        if (used) {
-            int64_t pos = (int64_t)lbase + wbase +
-                          __popcll(mask & ((1ull << lane) - 1ull));
+    d_block_compact(
+        cap, ngroups, [=](int64_t i) { return tab[i].key != AGG_EMPTY; },
+        [=](int64_t i, int64_t pos) {
             out[pos].key = tab[i].key;
             out[pos].key_isnull = 0;
             out[pos].count_star = (int64_t)tab[i].count_star;
             out[pos].count_v = (int64_t)tab[i].count_v;
             out[pos].sum_v = tab[i].sum_v;
             out[pos].sum_isnull = tab[i].count_v == 0;
-        }
-    }
-specials:
+        });
+    /* specials: the NULL-key and AGG_EMPTY-valued-key groups */
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (nullgrp->count_star > 0) {
             int64_t pos = (int64_t)atomicAdd((unsigned long long *)ngroups, 1ull);
@@ -1018,7 +884,13 @@ specials:
 template <typename T>
 __global__ void k_gather(const T *__restrict__ src,
                          const int64_t *__restrict__ perm, int64_t n,
-                         T *__restrict__ dst); /* defined in the exchange section */
+                         T *__restrict__ dst)
+{
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += stride)
+        dst[i] = src[perm[i]];
+}
 
 /* ---- partitioned aggregation (mid-cardinality; round-2 item 1) ----
  * When the distinct-key estimate exceeds what one block's LDS table can
@@ -2016,7 +1888,7 @@ static otbx_status agg_i64_run(const int64_t *keys, const uint8_t *knull,
                            dim3(256), 0, s, tab, cap_s);
         /* nullgrp sits at tab+cap (FULL cap), outside the small init */
         HIP_CHECK(hipMemsetAsync(nullgrp, 0, 2 * sizeof(agg_slot), s));
-        hipLaunchKernelGGL(k_agg_build_bounded, dim3(grid_for(n, 256)),
+        hipLaunchKernelGGL(k_agg_build<true>, dim3(grid_for(n, 256)),
                            dim3(256), 0, s, keys, knull, vals, vnull, n, tab,
                            cap_s, nullgrp, d_ab);
         HIP_CHECK(hipMemcpyAsync(h_ab, d_ab, 4, hipMemcpyDeviceToHost, s));
@@ -2026,13 +1898,14 @@ static otbx_status agg_i64_run(const int64_t *keys, const uint8_t *knull,
         } else {
             hipLaunchKernelGGL(k_agg_init, dim3(grid_for(cap + 2, 256)),
                                dim3(256), 0, s, tab, cap + 2);
-            hipLaunchKernelGGL(k_agg_build, dim3(grid_for(n, 256)), dim3(256),
-                               0, s, keys, knull, vals, vnull, n, tab, cap,
-                               nullgrp);
+            hipLaunchKernelGGL(k_agg_build<false>, dim3(grid_for(n, 256)),
+                               dim3(256), 0, s, keys, knull, vals, vnull, n,
+                               tab, cap, nullgrp, (unsigned int *)nullptr);
         }
     } else {
-        hipLaunchKernelGGL(k_agg_build, dim3(grid_for(n, 256)), dim3(256), 0,
-                           s, keys, knull, vals, vnull, n, tab, cap, nullgrp);
+        hipLaunchKernelGGL(k_agg_build<false>, dim3(grid_for(n, 256)),
+                           dim3(256), 0, s, keys, knull, vals, vnull, n, tab,
+                           cap, nullgrp, (unsigned int *)nullptr);
     }
     if (compact_tab)
         hipLaunchKernelGGL(k_agg_compact, dim3(grid_for(cap, 256)), dim3(256),
@@ -2436,7 +2309,29 @@ otbx_status otbx_agg_i64_var(const int64_t *keys, const uint8_t *knull,
 
 __global__ void k_minmax_i64(const int64_t *__restrict__ keys, int64_t n,
                              unsigned long long *minkey,
-                             unsigned long long *maxkey); /* defined below */
+                             unsigned long long *maxkey)
+{
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    unsigned long long mymin = ~0ull >> 1, mymax = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        unsigned long long k = (unsigned long long)keys[i];
+        if (k < mymin) mymin = k;
+        if (k > mymax) mymax = k;
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+        unsigned long long mn = (unsigned long long)__shfl_down(
+            (long long)mymin, off, WAVE);
+        unsigned long long mx = (unsigned long long)__shfl_down(
+            (long long)mymax, off, WAVE);
+        if (mn < mymin) mymin = mn;
+        if (mx > mymax) mymax = mx;
+    }
+    if ((threadIdx.x % WAVE) == 0) {
+        if (mymin != (~0ull >> 1)) atomicMin(minkey, mymin);
+        if (mymax) atomicMax(maxkey, mymax);
+    }
+}
 
 /* part bitmap for partkey slice [lo, hi): dense p_partkey 1..nparts, bit
  * (idx - lo) set where p_type % typemod == typeval (the p_name LIKE filter
@@ -3246,17 +3141,6 @@ __global__ void k_part_scatter(const int64_t *__restrict__ keys, int64_t n,
         unsigned int off = atomicAdd(&lcur[owner], 1u);
         perm[base[owner] + off] = i;
     }
-}
-
-template <typename T>
-__global__ void k_gather(const T *__restrict__ src,
-                         const int64_t *__restrict__ perm, int64_t n,
-                         T *__restrict__ dst)
-{
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += stride)
-        dst[i] = src[perm[i]];
 }
 
 extern "C" {
@@ -5067,32 +4951,6 @@ __global__ void k_count_customer_seg(const otbx_customer_dev c, uint8_t want,
     }
 }
 
-__global__ void k_minmax_i64(const int64_t *__restrict__ keys, int64_t n,
-                             unsigned long long *minkey,
-                             unsigned long long *maxkey)
-{
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    unsigned long long mymin = ~0ull >> 1, mymax = 0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += stride) {
-        unsigned long long k = (unsigned long long)keys[i];
-        if (k < mymin) mymin = k;
-        if (k > mymax) mymax = k;
-    }
-    for (int off = WAVE / 2; off > 0; off >>= 1) {
-        unsigned long long mn = (unsigned long long)__shfl_down(
-            (long long)mymin, off, WAVE);
-        unsigned long long mx = (unsigned long long)__shfl_down(
-            (long long)mymax, off, WAVE);
-        if (mn < mymin) mymin = mn;
-        if (mx > mymax) mymax = mx;
-    }
-    if ((threadIdx.x % WAVE) == 0) {
-        if (mymin != (~0ull >> 1)) atomicMin(minkey, mymin);
-        if (mymax) atomicMax(maxkey, mymax);
-    }
-}
-
 /* customer-key bitmap build (dense-custkey direct filter; 1-2 MB and
  * L2-resident vs a 64+ MB hashed keyset — same reasoning as the orderkey
  * direct path) */
@@ -5733,6 +5591,92 @@ static int64_t nk_estimate_groups(const otbx_keyset &ks, int64_t n,
 
 #define NK_PROBE_BOUND 128
 
+/* ---- claim-by-row-index aggregate table (agg2 / aggn; dec_slot below has
+ * the same claim word with a 128-bit sum) ---- */
+struct claim_slot {
+    long long idx; /* claim word: -1 empty, else defining row index */
+    unsigned long long count_star;
+    unsigned long long count_v;
+    double sum;
+};
+
+__global__ void k_claim_init(claim_slot *tab, int64_t cap)
+{
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < cap;
+         i += stride) {
+        tab[i].idx = -1;
+        tab[i].count_star = 0;
+        tab[i].count_v = 0;
+        tab[i].sum = 0.0;
+    }
+}
+
+/* the 4-byte abort flag and its pinned host mirror, shared by the three
+ * aggregates (calls are serial per process — otbx.h) */
+static otbx_status nk_abort_words(unsigned int **d_ab, unsigned int **h_ab)
+{
+    static unsigned int *d = nullptr;
+    static unsigned int *h = nullptr;
+    if (!d) {
+        SCR_ALLOC_DEV(d, 4);
+        SCR_ALLOC_HOST(h, 4);
+    }
+    *d_ab = d;
+    *h_ab = h;
+    return OTBX_OK;
+}
+
+/* Driver of the claim-slot aggregates. Estimator-sized attempt first (the
+ * 1-key recipe: a full-n table is probe- and init/compact-heavy when
+ * groups << rows), bounded by the abort flag; if the flag comes back set
+ * (rare-tail overflow) everything is redone against the full cap-slot
+ * table. init(c) and compact(c) launch over a c-slot table, build(c, abortf)
+ * over the n rows; one stream sync per bounded attempt. stab is the
+ * estimator's AGG_SCAP-entry sample table. */
+template <typename Init, typename Build, typename Compact>
+static otbx_status nk_bounded_agg(const otbx_keyset &ks, int64_t n,
+                                  int64_t cap, int64_t *stab,
+                                  int64_t *ngroups_dev, hipStream_t s,
+                                  Init init, Build build, Compact compact)
+{
+    int64_t cap_use = cap;
+    if (n >= AGGP_THRESHOLD) {
+        int64_t est = nk_estimate_groups(ks, n, stab, s);
+        int64_t cs = next_pow2_host(est * 8 < 4096 ? 4096 : est * 8);
+        if (cs < cap) cap_use = cs;
+    }
+    const char *fcap = getenv("OTBX_NK_FORCE_CAP"); /* test hook: force a
+        tiny first-attempt table so the abort+full-rerun path executes */
+    if (fcap) {
+        int64_t v = atoll(fcap);
+        if (v >= 16 && v < cap)
+            cap_use = next_pow2_host(v);
+    }
+    unsigned int *d_ab, *h_ab;
+    otbx_status st = nk_abort_words(&d_ab, &h_ab);
+    if (st != OTBX_OK)
+        return st;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        bool bounded = cap_use < cap;
+        HIP_CHECK(hipMemsetAsync(ngroups_dev, 0, 8, s));
+        HIP_CHECK(hipMemsetAsync(d_ab, 0, 4, s));
+        init(cap_use);
+        if (n > 0)
+            build(cap_use, bounded ? d_ab : (unsigned int *)NULL);
+        if (!bounded)
+            break;
+        HIP_CHECK(hipMemcpyAsync(h_ab, d_ab, 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (!*h_ab)
+            break;
+        cap_use = cap; /* rare-tail overflow: redo against the full table */
+    }
+    compact(cap_use);
+    HIP_CHECK(hipGetLastError());
+    return OTBX_OK;
+}
+
 /* ================= extended joins (otbx_join_i64_ext / _i64x2) ===========
  * The HJ_* fill-state FSM (nodeHashjoin.c:139-144) on the generic open-
  * addressing join: inner/left/semi/anti/right/full, optionally on a
@@ -6023,32 +5967,13 @@ __global__ void k_joinx_fill_probe(const uint8_t *__restrict__ n1,
  * slot's group. Aggregates as otbx_agg_i64: count(*), count(v), sum(v)
  * (avg = sum/count; the GPU keeps [N, Sx] — include/otbx.h note). */
 
-struct agg2_slot {
-    long long idx; /* claim word: -1 empty, else defining row index */
-    unsigned long long count_star;
-    unsigned long long count_v;
-    double sum;
-};
-
-__global__ void k_agg2_init(agg2_slot *tab, int64_t cap)
-{
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < cap;
-         i += stride) {
-        tab[i].idx = -1;
-        tab[i].count_star = 0;
-        tab[i].count_v = 0;
-        tab[i].sum = 0.0;
-    }
-}
-
 __global__ void k_agg2_build(const int64_t *__restrict__ k1,
                              const uint8_t *__restrict__ n1,
                              const int64_t *__restrict__ k2,
                              const uint8_t *__restrict__ n2,
                              const double *__restrict__ vals,
                              const uint8_t *__restrict__ vnull, int64_t n,
-                             agg2_slot *tab, int64_t cap,
+                             claim_slot *tab, int64_t cap,
                              unsigned int *abortf)
 {
     int64_t mask = cap - 1;
@@ -6093,7 +6018,7 @@ __global__ void k_agg2_build(const int64_t *__restrict__ k1,
     }
 }
 
-__global__ void k_agg2_compact(const agg2_slot *__restrict__ tab, int64_t cap,
+__global__ void k_agg2_compact(const claim_slot *__restrict__ tab, int64_t cap,
                                const int64_t *__restrict__ k1,
                                const uint8_t *__restrict__ n1,
                                const int64_t *__restrict__ k2,
@@ -6101,44 +6026,9 @@ __global__ void k_agg2_compact(const agg2_slot *__restrict__ tab, int64_t cap,
                                otbx_agg2_group *__restrict__ out,
                                int64_t *ngroups)
 {
-    /* block-aggregated two-phase emission — ONE global reservation per
-     * block (the k_agg_compact recipe; a per-wave wave_append over a
-     * large slot scan serializes on the single group counter). */
-    __shared__ unsigned long long lbase;
-    __shared__ unsigned int lcnt, ltot;
-    if (threadIdx.x == 0) lcnt = 0;
-    __syncthreads();
-    int64_t per_block = (cap + gridDim.x - 1) / gridDim.x;
-    int64_t lo = blockIdx.x * per_block;
-    int64_t hi = lo + per_block < cap ? lo + per_block : cap;
-    int lane = (int)(threadIdx.x % WAVE);
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        unsigned long long mask = __ballot(tab[i].idx >= 0);
-        if (lane == 0 && mask)
-            atomicAdd(&lcnt, (unsigned int)__popcll(mask));
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ltot = lcnt;
-        lbase = lcnt ? (unsigned long long)atomicAdd(
-                           (unsigned long long *)ngroups,
-                           (unsigned long long)lcnt)
-                     : 0;
-        lcnt = 0;
-    }
-    __syncthreads();
-    if (ltot == 0) return;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        bool used = tab[i].idx >= 0;
-        unsigned long long mask = __ballot(used);
-        if (!mask) continue;
-        unsigned int wbase = 0;
-        if (lane == 0)
-            wbase = atomicAdd(&lcnt, (unsigned int)__popcll(mask));
-        wbase = (unsigned int)__shfl((int)wbase, 0, WAVE);
-        if (used) {
-            int64_t pos = (int64_t)lbase + wbase +
-                          __popcll(mask & ((1ull << lane) - 1ull));
+    d_block_compact(
+        cap, ngroups, [=](int64_t i) { return tab[i].idx >= 0; },
+        [=](int64_t i, int64_t pos) {
             long long r = tab[i].idx;
             bool in1 = n1 && n1[r], in2 = n2 && n2[r];
             out[pos].key1 = in1 ? 0 : k1[r];
@@ -6150,8 +6040,7 @@ __global__ void k_agg2_compact(const agg2_slot *__restrict__ tab, int64_t cap,
             out[pos].key2_isnull = in2;
             out[pos].sum_isnull = tab[i].count_v == 0;
             out[pos]._pad = 0;
-        }
-    }
+        });
 }
 
 extern "C" {
@@ -6318,7 +6207,7 @@ otbx_status otbx_agg_i64x2_workspace_bytes(int64_t n, size_t *bytes)
 {
     /* full-cap table (the abort-fallback path) + the estimator's sample
      * table (AGG_SCAP i64 hashes) */
-    *bytes = (size_t)jx_cap_for(n) * sizeof(agg2_slot) +
+    *bytes = (size_t)jx_cap_for(n) * sizeof(claim_slot) +
              (size_t)AGG_SCAP * 8;
     return OTBX_OK;
 }
@@ -6338,57 +6227,28 @@ otbx_status otbx_agg_i64x2(const int64_t *k1, const uint8_t *k1null,
     otbx_agg_i64x2_workspace_bytes(n, &need);
     if (ws_bytes < need)
         return OTBX_ERR_INVALID;
-    agg2_slot *tab = (agg2_slot *)ws;
-    int64_t *stab = (int64_t *)((char *)ws + (size_t)cap * sizeof(agg2_slot));
-    /* estimator-sized attempt first (1-key recipe): the full-n table is
-     * probe- and init/compact-heavy when groups << rows */
-    int64_t cap_use = cap;
-    if (n >= AGGP_THRESHOLD) {
-        otbx_keyset ks;
-        ks.nkeys = 2;
-        ks.keys[0] = k1; ks.keys[1] = k2;
-        ks.nulls[0] = k1null; ks.nulls[1] = k2null;
-        int64_t est = nk_estimate_groups(ks, n, stab, s);
-        int64_t cs = next_pow2_host(est * 8 < 4096 ? 4096 : est * 8);
-        if (cs < cap) cap_use = cs;
-    }
-    const char *fcap = getenv("OTBX_NK_FORCE_CAP"); /* test hook: force a
-        tiny first-attempt table so the abort+full-rerun path executes */
-    if (fcap) {
-        int64_t v = atoll(fcap);
-        if (v >= 16 && v < cap)
-            cap_use = next_pow2_host(v);
-    }
-    static unsigned int *d_ab2 = nullptr;
-    static unsigned int *h_ab2 = nullptr;
-    if (!d_ab2) {
-        SCR_ALLOC_DEV(d_ab2, 4);
-        SCR_ALLOC_HOST(h_ab2, 4);
-    }
-    for (int attempt = 0; attempt < 2; attempt++) {
-        bool bounded = cap_use < cap;
-        HIP_CHECK(hipMemsetAsync(ngroups_dev, 0, 8, s));
-        HIP_CHECK(hipMemsetAsync(d_ab2, 0, 4, s));
-        hipLaunchKernelGGL(k_agg2_init, dim3(grid_for(cap_use, 256)),
-                           dim3(256), 0, s, tab, cap_use);
-        if (n > 0)
+    claim_slot *tab = (claim_slot *)ws;
+    int64_t *stab = (int64_t *)((char *)ws + (size_t)cap * sizeof(claim_slot));
+    otbx_keyset ks;
+    ks.nkeys = 2;
+    ks.keys[0] = k1; ks.keys[1] = k2;
+    ks.nulls[0] = k1null; ks.nulls[1] = k2null;
+    return nk_bounded_agg(
+        ks, n, cap, stab, ngroups_dev, s,
+        [&](int64_t c) {
+            hipLaunchKernelGGL(k_claim_init, dim3(grid_for(c, 256)),
+                               dim3(256), 0, s, tab, c);
+        },
+        [&](int64_t c, unsigned int *abortf) {
             hipLaunchKernelGGL(k_agg2_build, dim3(grid_for(n, 256)),
                                dim3(256), 0, s, k1, k1null, k2, k2null, vals,
-                               val_null, n, tab, cap_use,
-                               bounded ? d_ab2 : NULL);
-        if (!bounded)
-            break;
-        HIP_CHECK(hipMemcpyAsync(h_ab2, d_ab2, 4, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (!*h_ab2)
-            break;
-        cap_use = cap; /* rare-tail overflow: redo against the full table */
-    }
-    hipLaunchKernelGGL(k_agg2_compact, dim3(grid_for(cap_use, 256)),
-                       dim3(256), 0, s, tab, cap_use, k1, k1null, k2, k2null,
-                       groups_dev, ngroups_dev);
-    HIP_CHECK(hipGetLastError());
-    return OTBX_OK;
+                               val_null, n, tab, c, abortf);
+        },
+        [&](int64_t c) {
+            hipLaunchKernelGGL(k_agg2_compact, dim3(grid_for(c, 256)),
+                               dim3(256), 0, s, tab, c, k1, k1null, k2,
+                               k2null, groups_dev, ngroups_dev);
+        });
 }
 
 otbx_status otbx_build_q9recs(const otbx_lineitem_dev *l, void *recs_dev,
@@ -6491,44 +6351,9 @@ __global__ void k_dec_compact(const dec_slot *__restrict__ tab, int64_t cap,
                               otbx_dec_group *__restrict__ out,
                               int64_t *ngroups)
 {
-    /* block-aggregated two-phase emission — ONE global reservation per
-     * block (the k_agg_compact recipe; a per-wave wave_append over a
-     * large slot scan serializes on the single group counter). */
-    __shared__ unsigned long long lbase;
-    __shared__ unsigned int lcnt, ltot;
-    if (threadIdx.x == 0) lcnt = 0;
-    __syncthreads();
-    int64_t per_block = (cap + gridDim.x - 1) / gridDim.x;
-    int64_t lo = blockIdx.x * per_block;
-    int64_t hi = lo + per_block < cap ? lo + per_block : cap;
-    int lane = (int)(threadIdx.x % WAVE);
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        unsigned long long mask = __ballot(tab[i].idx >= 0);
-        if (lane == 0 && mask)
-            atomicAdd(&lcnt, (unsigned int)__popcll(mask));
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ltot = lcnt;
-        lbase = lcnt ? (unsigned long long)atomicAdd(
-                           (unsigned long long *)ngroups,
-                           (unsigned long long)lcnt)
-                     : 0;
-        lcnt = 0;
-    }
-    __syncthreads();
-    if (ltot == 0) return;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        bool used = tab[i].idx >= 0;
-        unsigned long long mask = __ballot(used);
-        if (!mask) continue;
-        unsigned int wbase = 0;
-        if (lane == 0)
-            wbase = atomicAdd(&lcnt, (unsigned int)__popcll(mask));
-        wbase = (unsigned int)__shfl((int)wbase, 0, WAVE);
-        if (used) {
-            int64_t pos = (int64_t)lbase + wbase +
-                          __popcll(mask & ((1ull << lane) - 1ull));
+    d_block_compact(
+        cap, ngroups, [=](int64_t i) { return tab[i].idx >= 0; },
+        [=](int64_t i, int64_t pos) {
             long long r = tab[i].idx;
             bool kn = knull && knull[r];
             out[pos].key = kn ? 0 : keys[r];
@@ -6538,8 +6363,7 @@ __global__ void k_dec_compact(const dec_slot *__restrict__ tab, int64_t cap,
             out[pos].sum_lo = tab[i].sum_lo;
             out[pos].key_isnull = kn;
             out[pos].sum_isnull = tab[i].count_v == 0;
-        }
-    }
+        });
 }
 
 extern "C" {
@@ -6567,52 +6391,26 @@ otbx_status otbx_agg_i64_dec(const int64_t *keys, const uint8_t *knull,
         return OTBX_ERR_INVALID;
     dec_slot *tab = (dec_slot *)ws;
     int64_t *stab = (int64_t *)((char *)ws + (size_t)cap * sizeof(dec_slot));
-    int64_t cap_use = cap;
-    if (n >= AGGP_THRESHOLD) {
-        otbx_keyset ks;
-        ks.nkeys = 1;
-        ks.keys[0] = keys;
-        ks.nulls[0] = knull;
-        int64_t est = nk_estimate_groups(ks, n, stab, s);
-        int64_t cs = next_pow2_host(est * 8 < 4096 ? 4096 : est * 8);
-        if (cs < cap) cap_use = cs;
-    }
-    const char *fcap = getenv("OTBX_NK_FORCE_CAP"); /* test hook: force a
-        tiny first-attempt table so the abort+full-rerun path executes */
-    if (fcap) {
-        int64_t v = atoll(fcap);
-        if (v >= 16 && v < cap)
-            cap_use = next_pow2_host(v);
-    }
-    static unsigned int *d_abd = nullptr;
-    static unsigned int *h_abd = nullptr;
-    if (!d_abd) {
-        SCR_ALLOC_DEV(d_abd, 4);
-        SCR_ALLOC_HOST(h_abd, 4);
-    }
-    for (int attempt = 0; attempt < 2; attempt++) {
-        bool bounded = cap_use < cap;
-        HIP_CHECK(hipMemsetAsync(ngroups_dev, 0, 8, s));
-        HIP_CHECK(hipMemsetAsync(d_abd, 0, 4, s));
-        hipLaunchKernelGGL(k_dec_init, dim3(grid_for(cap_use, 256)),
-                           dim3(256), 0, s, tab, cap_use);
-        if (n > 0)
+    otbx_keyset ks;
+    ks.nkeys = 1;
+    ks.keys[0] = keys;
+    ks.nulls[0] = knull;
+    return nk_bounded_agg(
+        ks, n, cap, stab, ngroups_dev, s,
+        [&](int64_t c) {
+            hipLaunchKernelGGL(k_dec_init, dim3(grid_for(c, 256)), dim3(256),
+                               0, s, tab, c);
+        },
+        [&](int64_t c, unsigned int *abortf) {
             hipLaunchKernelGGL(k_dec_build, dim3(grid_for(n, 256)),
                                dim3(256), 0, s, keys, knull, vals, vnull, n,
-                               tab, cap_use, bounded ? d_abd : NULL);
-        if (!bounded)
-            break;
-        HIP_CHECK(hipMemcpyAsync(h_abd, d_abd, 4, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (!*h_abd)
-            break;
-        cap_use = cap;
-    }
-    hipLaunchKernelGGL(k_dec_compact, dim3(grid_for(cap_use, 256)),
-                       dim3(256), 0, s, tab, cap_use, keys, knull,
-                       groups_dev, ngroups_dev);
-    HIP_CHECK(hipGetLastError());
-    return OTBX_OK;
+                               tab, c, abortf);
+        },
+        [&](int64_t c) {
+            hipLaunchKernelGGL(k_dec_compact, dim3(grid_for(c, 256)),
+                               dim3(256), 0, s, tab, c, keys, knull,
+                               groups_dev, ngroups_dev);
+        });
 }
 
 __global__ void k_build_key32(const int64_t *__restrict__ src, int64_t n,
@@ -6662,29 +6460,10 @@ otbx_status otbx_build_key32(const int64_t *src, int64_t n, int32_t *dst,
  * Slots claim by defining row index (execGrouping.c firstTuple pattern);
  * identity compares run over the keyset columns. Generality tier. */
 
-struct aggn_slot {
-    long long idx; /* claim word: -1 empty, else defining row index */
-    unsigned long long count_star;
-    unsigned long long count_v;
-    double sum;
-};
-
-__global__ void k_aggn_init(aggn_slot *tab, int64_t cap)
-{
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < cap;
-         i += stride) {
-        tab[i].idx = -1;
-        tab[i].count_star = 0;
-        tab[i].count_v = 0;
-        tab[i].sum = 0.0;
-    }
-}
-
 __global__ void k_aggn_build(const otbx_keyset ks,
                              const double *__restrict__ vals,
                              const uint8_t *__restrict__ vnull, int64_t n,
-                             aggn_slot *tab, int64_t cap,
+                             claim_slot *tab, int64_t cap,
                              unsigned int *abortf)
 {
     int64_t mask = cap - 1;
@@ -6722,56 +6501,20 @@ __global__ void k_aggn_build(const otbx_keyset ks,
     }
 }
 
-__global__ void k_aggn_compact(const aggn_slot *__restrict__ tab, int64_t cap,
+__global__ void k_aggn_compact(const claim_slot *__restrict__ tab, int64_t cap,
                                otbx_aggn_group *__restrict__ out,
                                int64_t *ngroups)
 {
-    /* block-aggregated two-phase emission — ONE global reservation per
-     * block (the k_agg_compact recipe; a per-wave wave_append over a
-     * large slot scan serializes on the single group counter). */
-    __shared__ unsigned long long lbase;
-    __shared__ unsigned int lcnt, ltot;
-    if (threadIdx.x == 0) lcnt = 0;
-    __syncthreads();
-    int64_t per_block = (cap + gridDim.x - 1) / gridDim.x;
-    int64_t lo = blockIdx.x * per_block;
-    int64_t hi = lo + per_block < cap ? lo + per_block : cap;
-    int lane = (int)(threadIdx.x % WAVE);
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        unsigned long long mask = __ballot(tab[i].idx >= 0);
-        if (lane == 0 && mask)
-            atomicAdd(&lcnt, (unsigned int)__popcll(mask));
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ltot = lcnt;
-        lbase = lcnt ? (unsigned long long)atomicAdd(
-                           (unsigned long long *)ngroups,
-                           (unsigned long long)lcnt)
-                     : 0;
-        lcnt = 0;
-    }
-    __syncthreads();
-    if (ltot == 0) return;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        bool used = tab[i].idx >= 0;
-        unsigned long long mask = __ballot(used);
-        if (!mask) continue;
-        unsigned int wbase = 0;
-        if (lane == 0)
-            wbase = atomicAdd(&lcnt, (unsigned int)__popcll(mask));
-        wbase = (unsigned int)__shfl((int)wbase, 0, WAVE);
-        if (used) {
-            int64_t pos = (int64_t)lbase + wbase +
-                          __popcll(mask & ((1ull << lane) - 1ull));
+    d_block_compact(
+        cap, ngroups, [=](int64_t i) { return tab[i].idx >= 0; },
+        [=](int64_t i, int64_t pos) {
             out[pos].row_idx = tab[i].idx;
             out[pos].count_star = (int64_t)tab[i].count_star;
             out[pos].count_v = (int64_t)tab[i].count_v;
             out[pos].sum_v = tab[i].sum;
             out[pos].sum_isnull = tab[i].count_v == 0;
             out[pos]._pad = 0;
-        }
-    }
+        });
 }
 
 /* N-key join: same structure as k_joinx_* but identity through keysets */
@@ -6953,7 +6696,7 @@ static bool keyset_ok(const otbx_keyset *ks)
 
 otbx_status otbx_agg_i64n_workspace_bytes(int64_t n, size_t *bytes)
 {
-    *bytes = (size_t)jx_cap_for(n) * sizeof(aggn_slot) +
+    *bytes = (size_t)jx_cap_for(n) * sizeof(claim_slot) +
              (size_t)AGG_SCAP * 8; /* + estimator sample table */
     return OTBX_OK;
 }
@@ -6971,50 +6714,24 @@ otbx_status otbx_agg_i64n(const otbx_keyset *ks, const double *vals,
     otbx_agg_i64n_workspace_bytes(n, &need);
     if (ws_bytes < need)
         return OTBX_ERR_INVALID;
-    aggn_slot *tab = (aggn_slot *)ws;
-    int64_t *stab = (int64_t *)((char *)ws + (size_t)cap * sizeof(aggn_slot));
-    int64_t cap_use = cap;
-    if (n >= AGGP_THRESHOLD) {
-        int64_t est = nk_estimate_groups(*ks, n, stab, s);
-        int64_t cs = next_pow2_host(est * 8 < 4096 ? 4096 : est * 8);
-        if (cs < cap) cap_use = cs;
-    }
-    const char *fcap = getenv("OTBX_NK_FORCE_CAP"); /* test hook: force a
-        tiny first-attempt table so the abort+full-rerun path executes */
-    if (fcap) {
-        int64_t v = atoll(fcap);
-        if (v >= 16 && v < cap)
-            cap_use = next_pow2_host(v);
-    }
-    static unsigned int *d_abn = nullptr;
-    static unsigned int *h_abn = nullptr;
-    if (!d_abn) {
-        SCR_ALLOC_DEV(d_abn, 4);
-        SCR_ALLOC_HOST(h_abn, 4);
-    }
-    for (int attempt = 0; attempt < 2; attempt++) {
-        bool bounded = cap_use < cap;
-        HIP_CHECK(hipMemsetAsync(ngroups_dev, 0, 8, s));
-        HIP_CHECK(hipMemsetAsync(d_abn, 0, 4, s));
-        hipLaunchKernelGGL(k_aggn_init, dim3(grid_for(cap_use, 256)),
-                           dim3(256), 0, s, tab, cap_use);
-        if (n > 0)
+    claim_slot *tab = (claim_slot *)ws;
+    int64_t *stab = (int64_t *)((char *)ws + (size_t)cap * sizeof(claim_slot));
+    return nk_bounded_agg(
+        *ks, n, cap, stab, ngroups_dev, s,
+        [&](int64_t c) {
+            hipLaunchKernelGGL(k_claim_init, dim3(grid_for(c, 256)),
+                               dim3(256), 0, s, tab, c);
+        },
+        [&](int64_t c, unsigned int *abortf) {
             hipLaunchKernelGGL(k_aggn_build, dim3(grid_for(n, 256)),
-                               dim3(256), 0, s, *ks, vals, vnull, n, tab,
-                               cap_use, bounded ? d_abn : NULL);
-        if (!bounded)
-            break;
-        HIP_CHECK(hipMemcpyAsync(h_abn, d_abn, 4, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (!*h_abn)
-            break;
-        cap_use = cap;
-    }
-    hipLaunchKernelGGL(k_aggn_compact, dim3(grid_for(cap_use, 256)),
-                       dim3(256), 0, s, tab, cap_use, groups_dev,
-                       ngroups_dev);
-    HIP_CHECK(hipGetLastError());
-    return OTBX_OK;
+                               dim3(256), 0, s, *ks, vals, vnull, n, tab, c,
+                               abortf);
+        },
+        [&](int64_t c) {
+            hipLaunchKernelGGL(k_aggn_compact, dim3(grid_for(c, 256)),
+                               dim3(256), 0, s, tab, c, groups_dev,
+                               ngroups_dev);
+        });
 }
 
 otbx_status otbx_join_i64n_workspace_bytes(int64_t nb, int64_t np,

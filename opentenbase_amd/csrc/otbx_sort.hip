@@ -25,24 +25,8 @@
  *     compacted IN ROW ORDER, and only those are sorted. The row count the
  *     sort kernels see (ss_state.m) lives on the device.
  */
-#include <hip/hip_runtime.h>
-#include <limits.h>
-#include <stdio.h>
-
-#include "../../include/otbx.h"
+#include "otbx_common.h"
 #include "otbx_sortkey.h"   /* ss_norm: the normalised key */
-
-#define WAVE 64
-
-#define HIP_CHECK(x)                                                     \
-    do {                                                                 \
-        hipError_t err_ = (x);                                           \
-        if (err_ != hipSuccess) {                                        \
-            fprintf(stderr, "otbx: HIP error %s at %s:%d\n",             \
-                    hipGetErrorString(err_), __FILE__, __LINE__);        \
-            return OTBX_ERR_HIP;                                         \
-        }                                                                \
-    } while (0)
 
 #define SS_THREADS 256
 #define SS_WAVES (SS_THREADS / WAVE)
@@ -651,8 +635,6 @@ struct ss_layout {
     uint32_t chunks;  /* scan chunks at capacity */
 };
 
-static inline size_t ss_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static void ss_plan_layout(int64_t n, ss_layout *L)
 {
     const size_t nal = ((size_t)n + 63) & ~(size_t)63;
@@ -660,21 +642,13 @@ static void ss_plan_layout(int64_t n, ss_layout *L)
     L->chunks = (uint32_t)(((size_t)SS_BINS * L->nb + SS_SCAN_CHUNK - 1) /
                            SS_SCAN_CHUNK);
     size_t o = SS_HEADER_BYTES;
-    L->keyA = o; o += ss_al(nal * 8);
-    L->keyB = o; o += ss_al(nal * 8);
-    L->idxA = o; o += ss_al(nal * 4);
-    L->idxB = o; o += ss_al(nal * 4);
-    L->hist = o; o += ss_al((size_t)SS_BINS * L->nb * 4);
-    L->sums = o; o += ss_al((size_t)L->chunks * 4);
+    L->keyA = o; o += align256_sz(nal * 8);
+    L->keyB = o; o += align256_sz(nal * 8);
+    L->idxA = o; o += align256_sz(nal * 4);
+    L->idxB = o; o += align256_sz(nal * 4);
+    L->hist = o; o += align256_sz((size_t)SS_BINS * L->nb * 4);
+    L->sums = o; o += align256_sz((size_t)L->chunks * 4);
     L->total = o;
-}
-
-static inline int ss_grid(int64_t work, int block)
-{
-    int64_t g = (work + block - 1) / block;
-    if (g > 2048) g = 2048;
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 extern "C" {
@@ -736,7 +710,7 @@ otbx_status otbx_sort_perm(const otbx_sortspec *spec, int64_t n, int64_t limit,
     const bool select = limit > 0 && limit < n;
     const int64_t nout = select ? limit : n;
 
-    hipLaunchKernelGGL(k_ss_init, dim3(select ? 1 : ss_grid(n, 256)),
+    hipLaunchKernelGGL(k_ss_init, dim3(select ? 1 : grid_for(n, 256)),
                        dim3(256), 0, s, st, un, iA, select ? 0 : 1);
 
     if (select) {
@@ -746,7 +720,7 @@ otbx_status otbx_sort_perm(const otbx_sortspec *spec, int64_t n, int64_t limit,
         const int levels = (1 + wb + SS_LBITS - 1) / SS_LBITS > 5
                                ? 5 : (1 + wb + SS_LBITS - 1) / SS_LBITS;
         for (int lv = 0; lv < levels; lv++) {
-            hipLaunchKernelGGL(k_ss_lim_hist, dim3(ss_grid(n, SS_THREADS)),
+            hipLaunchKernelGGL(k_ss_lim_hist, dim3(grid_for(n, SS_THREADS)),
                                dim3(SS_THREADS), 0, s, st, k0, wb, un, lv);
             hipLaunchKernelGGL(k_ss_lim_thresh, dim3(1), dim3(SS_THREADS), 0,
                                s, st, (unsigned long long)limit);
@@ -772,7 +746,7 @@ otbx_status otbx_sort_perm(const otbx_sortspec *spec, int64_t n, int64_t limit,
         const int npass = ss_wbits(k.type) / 8;
         const int hasnull = k.nulls != nullptr;
         const uint32_t dnull = (k.flags & OTBX_SORT_NULLS_FIRST) ? 0u : 1u;
-        hipLaunchKernelGGL(k_ss_build, dim3(ss_grid(n, SS_THREADS)),
+        hipLaunchKernelGGL(k_ss_build, dim3(grid_for(n, SS_THREADS)),
                            dim3(SS_THREADS), 0, s, st, k, npass, un - 1, kA, kB,
                            iA, iB);
         hipLaunchKernelGGL(k_ss_plan, dim3(1), dim3(SS_THREADS), 0, s, st,
@@ -811,7 +785,7 @@ otbx_status otbx_sort_perm(const otbx_sortspec *spec, int64_t n, int64_t limit,
                                    hist);
         }
     }
-    hipLaunchKernelGGL(k_ss_emit, dim3(ss_grid(nout, 256)), dim3(256), 0, s,
+    hipLaunchKernelGGL(k_ss_emit, dim3(grid_for(nout, 256)), dim3(256), 0, s,
                        st, iA, iB, nout, perm_dev, nout_dev);
     HIP_CHECK(hipGetLastError());
     return OTBX_OK;

@@ -32,24 +32,8 @@
  * The sum is SEGMENTED: win_comb drops the left operand at a partition
  * start, so no value of one partition ever reaches another one.
  */
-#include <hip/hip_runtime.h>
-#include <limits.h>
-#include <stdio.h>
-
-#include "../../include/otbx.h"
+#include "otbx_common.h"
 #include "otbx_sortkey.h"   /* ss_norm: the normalised key */
-
-#define WAVE 64
-
-#define HIP_CHECK(x)                                                     \
-    do {                                                                 \
-        hipError_t err_ = (x);                                           \
-        if (err_ != hipSuccess) {                                        \
-            fprintf(stderr, "otbx: HIP error %s at %s:%d\n",             \
-                    hipGetErrorString(err_), __FILE__, __LINE__);        \
-            return OTBX_ERR_HIP;                                         \
-        }                                                                \
-    } while (0)
 
 #define WIN_THREADS 256
 #define WIN_WAVES (WIN_THREADS / WAVE)
@@ -635,19 +619,17 @@ struct win_layout {
     uint32_t ntiles;
 };
 
-static inline size_t win_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static void win_plan_layout(int64_t n, win_layout *L)
 {
     L->ntiles = (uint32_t)((n + WIN_TILE - 1) / WIN_TILE);
     const size_t padded = (size_t)L->ntiles * WIN_TILE;
     size_t o = 0;
-    L->flags = o; o += win_al(padded);
-    L->sval = o;  o += win_al(padded * 8);
-    L->rcnt = o;  o += win_al(padded * 4);
-    L->fend = o;  o += win_al(padded * 4);
-    L->tiles = o; o += win_al((size_t)L->ntiles * sizeof(win_tile));
-    L->carry = o; o += win_al((size_t)L->ntiles * sizeof(win_tile));
+    L->flags = o; o += align256_sz(padded);
+    L->sval = o;  o += align256_sz(padded * 8);
+    L->rcnt = o;  o += align256_sz(padded * 4);
+    L->fend = o;  o += align256_sz(padded * 4);
+    L->tiles = o; o += align256_sz((size_t)L->ntiles * sizeof(win_tile));
+    L->carry = o; o += align256_sz((size_t)L->ntiles * sizeof(win_tile));
     L->total = o;
 }
 

@@ -39,6 +39,36 @@ def test_every_header_symbol_exported(so):
     assert sorted(_lib.EXPORTED_SYMBOLS) == syms
 
 
+def _defined_dynamic_symbols(path):
+    import shutil
+    import subprocess
+    nm = shutil.which("nm")
+    if nm is None:
+        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+        for sub in ("llvm/bin/llvm-nm", "lib/llvm/bin/llvm-nm"):
+            cand = os.path.join(rocm, sub)
+            if os.path.exists(cand):
+                nm = cand
+                break
+    assert nm is not None, "neither nm nor ROCm's llvm-nm found"
+    out = subprocess.run([nm, "-D", "--defined-only", "--demangle", path],
+                         check=True, capture_output=True, text=True).stdout
+    # "<addr> <type> <name>"; a demangled C++ name carries its parameter list
+    names = [line.split(None, 2)[2] for line in out.splitlines()
+             if len(line.split(None, 2)) == 3]
+    return [n.split("(")[0].strip() for n in names]
+
+
+def test_no_private_otbx_symbol_exported(so):
+    """The otbx_* names the shared object defines (C names, and C++ functions
+    by their demangled name) are exactly the header's entry points: a
+    private host helper such as otbx_scr_alloc that is neither static nor
+    hidden fails here."""
+    exported = sorted(s for s in _defined_dynamic_symbols(_lib._SO)
+                      if s.startswith("otbx_"))
+    assert exported == header_symbols()
+
+
 def test_status_strings(so):
     for s in range(6):
         assert so.otbx_status_str(s)
