@@ -42,6 +42,10 @@
  *                            ExecWindowAgg (executor/nodeWindowAgg.c) with
  *                            row_number / rank / dense_rank and count / sum
  *                            over the default frame (windowfuncs.c:82-118)
+ *   otbx_filter_sel        — ExecScan/ExecQual for any qual shape: a CNF of
+ *                            typed, nullable comparisons (execScan.c:140,
+ *                            EEOP_QUAL execExprInterp.c:919) → the ordered
+ *                            selection vector the other operators gather by
  *   merge (Coordinator)    — NOT here: the shard merge (execFragment.c:3877)
  *                            is a collective over ranks, done by the host
  *                            layer with RCCL (torch.distributed) on the
@@ -641,6 +645,81 @@ otbx_status otbx_window(const otbx_sortspec *spec, int32_t npart,
                         const double *vals_dev, const uint8_t *val_null_dev,
                         void *ws_dev, size_t ws_bytes,
                         const otbx_window_out *out, void *stream);
+
+/* ---- generic GPU Filter: WHERE quals → ordered selection vector ----
+ * The ExecScan / ExecQual analog (executor/execScan.c:140-363 over the
+ * expression steps of executor/execExprInterp.c) for any qual in
+ * conjunctive normal form over typed, nullable columns: clauses are AND'ed,
+ * the terms of one clause are OR'ed, and a term is
+ *     col OP constant | col OP rcol | col IS NULL | col IS NOT NULL
+ * with OP one of = <> < <= > >=. Clause ids are non-decreasing along
+ * term[], so a clause is a run of adjacent terms. nterms == 0 selects every
+ * row (ExecQual with no qual returns true).
+ *
+ * RESULT: sel_dev[0 .. *nsel_dev) receives the passing row indices in
+ * ASCENDING order (order-preserving, deterministic compaction), int64 so
+ * it feeds otbx_gather_* unchanged; entries past *nsel_dev are not written.
+ * With sel_dev == NULL only the count is produced and the write pass is not
+ * launched (SELECT count(*) ... WHERE).
+ *
+ * SEMANTICS
+ *   - A row passes iff the whole qual is TRUE; NULL counts as failure
+ *     (EEOP_QUAL, execExprInterp.c:919).
+ *   - A comparison with a NULL operand is NULL (strict operator,
+ *     EEOP_FUNCEXPR_STRICT :703). AND / OR are Kleene (EEOP_BOOL_AND_STEP*
+ *     :783-838, EEOP_BOOL_OR_STEP* :850-904). There is no NOT above a term
+ *     and every operator has its complement, so this collapses to: a row
+ *     passes iff EVERY clause has AT LEAST ONE term that is TRUE, a term
+ *     being TRUE only when its operands are non-NULL and the comparison
+ *     holds.
+ *   - ISNULL / NOTNULL are never NULL (EEOP_NULLTEST_ISNULL :973); a column
+ *     without a mask has no NULLs.
+ *   - The value stored under a NULL never influences the result.
+ *   - I64 / I32 / U8: ordinary integer order; the column value is widened
+ *     to int64 and compared with `ci`, so a constant outside the column's
+ *     range is legal and compares mathematically (u8col < 256 is always
+ *     true, i32col = 2^40 never).
+ *   - F64: float8_cmp_internal (utils/adt/float.c:1172), exactly as
+ *     otbx_sort_perm orders — every NaN equals every NaN whatever its sign
+ *     or payload and is greater than every non-NaN, +Inf included;
+ *     -0.0 == +0.0 — for `cf` as well as for column values.
+ *
+ * Columns need only the natural alignment of their element type (a torch
+ * view such as col[1:] is a valid input); 16-byte-aligned columns take the
+ * vector-load path.
+ *
+ * Stream-ordered, no host synchronisation, nothing cached. Checked before
+ * any HIP call, each returning OTBX_ERR_INVALID: q or nsel_dev NULL; nterms
+ * outside 0..16; a type outside 0..3; an op outside 0..7; rcol set together
+ * with ISNULL / NOTNULL; rnulls set without rcol; decreasing clause ids;
+ * n < 0 or n > INT32_MAX; a NULL col with n > 0; ws_bytes below
+ * otbx_filter_workspace_bytes(n); ws_dev not 16-byte aligned. n == 0 is
+ * valid and writes *nsel_dev = 0. otbx_filter_workspace_bytes is pure host
+ * code and monotone in n (n/8 B of bitmask padded to whole tiles + 4 B per
+ * tile). sizeof(otbx_qualterm) == 64, sizeof(otbx_qual) == 1032. */
+enum { OTBX_CMP_EQ = 0, OTBX_CMP_NE, OTBX_CMP_LT, OTBX_CMP_LE, OTBX_CMP_GT,
+       OTBX_CMP_GE, OTBX_CMP_ISNULL, OTBX_CMP_NOTNULL };
+#define OTBX_MAX_QUAL_TERMS 16
+typedef struct {
+    const void    *col;     /* left operand: device column of `type`          */
+    const uint8_t *nulls;   /* byte per row, nonzero = NULL; may be NULL      */
+    const void    *rcol;    /* non-NULL: right operand is a column of the     */
+    const uint8_t *rnulls;  /*   SAME type (col OP rcol); NULL: a constant    */
+    int64_t        ci;      /* constant for I64 / I32 / U8 columns            */
+    double         cf;      /* constant for F64 columns                       */
+    int32_t        type;    /* OTBX_SORT_I64 / F64 / I32 / U8 (same codes)    */
+    int32_t        op;      /* OTBX_CMP_*                                     */
+    int32_t        clause;  /* terms with equal clause id are OR'ed           */
+    int32_t        _pad;
+} otbx_qualterm;
+typedef struct { int32_t nterms; otbx_qualterm term[OTBX_MAX_QUAL_TERMS]; } otbx_qual;
+
+otbx_status otbx_filter_workspace_bytes(int64_t n, size_t *bytes);
+otbx_status otbx_filter_sel(const otbx_qual *q, int64_t n,
+                            void *ws_dev, size_t ws_bytes,
+                            int64_t *sel_dev,   /* cap n; NULL = count only */
+                            int64_t *nsel_dev,  /* int64[1], required       */
+                            void *stream);
 
 /* ---- repartition exchange ----
  * The GPU half of the reference's "Distribute results by H: col" exchange

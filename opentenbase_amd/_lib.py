@@ -85,6 +85,20 @@ class WindowOutDev(C.Structure):
                 ("sum_isnull", C.c_void_p), ("part_rows", C.c_void_p)]
 
 
+class QualTermDev(C.Structure):
+    """otbx_qualterm (include/otbx.h): one comparison of a qual, 64 bytes."""
+    _fields_ = [("col", C.c_void_p), ("nulls", C.c_void_p),
+                ("rcol", C.c_void_p), ("rnulls", C.c_void_p),
+                ("ci", C.c_int64), ("cf", C.c_double),
+                ("type", C.c_int32), ("op", C.c_int32),
+                ("clause", C.c_int32), ("_pad", C.c_int32)]
+
+
+class QualDev(C.Structure):
+    """otbx_qual: up to 16 terms in conjunctive normal form, 1032 bytes."""
+    _fields_ = [("nterms", C.c_int32), ("term", QualTermDev * 16)]
+
+
 class PartDev(C.Structure):
     _fields_ = [
         ("n", C.c_int64),
@@ -121,6 +135,7 @@ def lib():
         _lib.otbx_q9_workspace_bytes.argtypes = [i64, i64, i64, u32, szp]
         _lib.otbx_sort_workspace_bytes.argtypes = [i64, C.c_int32, i64, szp]
         _lib.otbx_window_workspace_bytes.argtypes = [i64, szp]
+        _lib.otbx_filter_workspace_bytes.argtypes = [i64, szp]
     return _lib
 
 
@@ -156,4 +171,5 @@ EXPORTED_SYMBOLS = [
     "otbx_join_i64n_workspace_bytes", "otbx_join_i64n",
     "otbx_sort_workspace_bytes", "otbx_sort_perm",
     "otbx_window_workspace_bytes", "otbx_window",
+    "otbx_filter_workspace_bytes", "otbx_filter_sel",
 ]

@@ -3,7 +3,8 @@
  * (otbx_sort.hip) and the WindowAgg operator (otbx_window.hip). Both decide
  * "these two rows compare equal on this key" from the same (null digit,
  * normalised bits) pair, so partition / peer boundaries can never disagree
- * with the order the sort produced. Device code only.
+ * with the order the sort produced. The Filter operator (otbx_filter.hip)
+ * compares doubles on the same normalisation (ss_norm_f64). Device code only.
  */
 #ifndef OTBX_SORTKEY_H
 #define OTBX_SORTKEY_H
@@ -11,6 +12,20 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/otbx.h"
+
+/* float8_cmp_internal (utils/adt/float.c:1172) as an unsigned order: the
+ * returned bits compare (as uint64) exactly as the doubles do under it —
+ * every NaN one value above +Inf, -0 == +0. No direction, no NULLs: ss_norm
+ * adds those; the Filter operator (otbx_filter.hip) compares these directly. */
+__device__ __forceinline__ unsigned long long ss_norm_f64(double d)
+{
+    unsigned long long b = (unsigned long long)__double_as_longlong(d);
+    if (d != d)
+        b = 0x7ff8000000000000ull;  /* every NaN: one value, above +Inf */
+    else if (d == 0.0)
+        b = 0ull;                   /* -0 == +0 */
+    return (b >> 63) ? ~b : (b ^ 0x8000000000000000ull);
+}
 
 /* ---- key normalisation ----
  * returns the radix key (wbits wide, zero-extended) and the null digit:
@@ -31,16 +46,9 @@ ss_norm(const otbx_sortkey &k, uint32_t row, uint32_t *nulldigit)
         v = (unsigned long long)((const int64_t *)k.col)[row] ^
             0x8000000000000000ull;
         return desc ? ~v : v;
-    case OTBX_SORT_F64: {
-        const double d = ((const double *)k.col)[row];
-        unsigned long long b = (unsigned long long)__double_as_longlong(d);
-        if (d != d)
-            b = 0x7ff8000000000000ull;  /* every NaN: one value, above +Inf */
-        else if (d == 0.0)
-            b = 0ull;                   /* -0 == +0 */
-        v = (b >> 63) ? ~b : (b ^ 0x8000000000000000ull);
+    case OTBX_SORT_F64:
+        v = ss_norm_f64(((const double *)k.col)[row]);
         return desc ? ~v : v;
-    }
     case OTBX_SORT_I32:
         v = (unsigned long long)((uint32_t)((const int32_t *)k.col)[row] ^
                                  0x80000000u);

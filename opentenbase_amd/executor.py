@@ -17,8 +17,8 @@ import math
 import torch
 
 from ._lib import (CustomerDev, KeysetDev, LineitemDev, OrdersDev,
-                   OtbxError, PartDev, SortSpecDev, WindowOutDev, call, check,
-                   lib)
+                   OtbxError, PartDev, QualDev, SortSpecDev, WindowOutDev,
+                   call, check, lib)
 
 Q1_SLOT_ORDER = [(b"A", b"F"), (b"A", b"O"), (b"N", b"F"),
                  (b"N", b"O"), (b"R", b"F"), (b"R", b"O")]
@@ -801,6 +801,161 @@ def cume_dist(count_star, part_rows):
     out = np.asarray(count_star, dtype=np.float64) / \
         np.asarray(part_rows, dtype=np.float64)
     return float(out) if out.ndim == 0 else out
+
+
+CMP_OPS = {"=": 0, "<>": 1, "<": 2, "<=": 3, ">": 4, ">=": 5,
+           "isnull": 6, "notnull": 7}   # OTBX_CMP_*
+MAX_QUAL_TERMS = 16                     # OTBX_MAX_QUAL_TERMS
+
+
+class QualTerm:
+    """One term of a qual; build it with qual_term()."""
+    __slots__ = ("col", "op", "rhs", "nulls", "rnulls")
+
+    def __init__(self, col, op, rhs, nulls, rnulls):
+        self.col, self.op, self.rhs = col, op, rhs
+        self.nulls, self.rnulls = nulls, rnulls
+
+
+def qual_term(col, op, rhs=None, nulls=None, rnulls=None):
+    """col OP rhs as a term of GpuFilter's qual. col: device tensor of dtype
+    int64, float64, int32 or uint8. op: "=", "<>", "<", "<=", ">", ">=",
+    "isnull" or "notnull". rhs: a Python number (an int for the integer
+    dtypes), or a device tensor of col's dtype and length for a comparison
+    of two columns; None for the null tests. nulls / rnulls: optional uint8
+    null masks (nonzero = NULL) of col / of the rhs column."""
+    if op not in CMP_OPS:
+        raise OtbxError(3, f"filter: unknown operator {op!r}")
+    if not isinstance(col, torch.Tensor) or col.dtype not in _SORT_TYPE:
+        raise OtbxError(3, "filter: unsupported column dtype "
+                           f"{getattr(col, 'dtype', type(col))}")
+    n = len(col)
+    if op in ("isnull", "notnull"):
+        if rhs is not None or rnulls is not None:
+            raise OtbxError(3, f"filter: {op} takes no right operand")
+    elif isinstance(rhs, torch.Tensor):
+        if rhs.dtype != col.dtype:
+            raise OtbxError(3, f"filter: {col.dtype} column compared with a "
+                               f"{rhs.dtype} column")
+        if len(rhs) != n:
+            raise OtbxError(3, "filter: columns differ in length")
+    else:
+        if rnulls is not None:
+            raise OtbxError(3, "filter: rnulls without a right column")
+        if isinstance(rhs, bool) or not isinstance(rhs, (int, float)):
+            raise OtbxError(3, f"filter: {op} needs a number or a column")
+        if col.dtype != torch.float64:
+            if not isinstance(rhs, int):
+                raise OtbxError(3, "filter: integer column compared with a "
+                                   "non-integer constant")
+            if not -2**63 <= rhs < 2**63:
+                raise OtbxError(3, "filter: constant outside int64")
+    for m in (nulls, rnulls):
+        if m is not None and (m.dtype != torch.uint8 or len(m) != n):
+            raise OtbxError(3, "filter: a null mask is a uint8 tensor of the "
+                               "column's length")
+    return QualTerm(col, op, rhs, nulls, rnulls)
+
+
+class GpuFilter(CustomScanState):
+    """SeqScan's qual for any plan shape (ExecScan → ExecQual,
+    execScan.c:140): `clauses` is a list of lists of qual_term() terms, the
+    AND of ORs; [] is no qual and selects every row (pass n then). At most
+    16 terms in all. Yields ONE tuple: the int64 selection tensor — the
+    passing row indices in ascending order — or, with count_only, the count
+    (the selection is never written). `.count` holds the count after the
+    run; gather(col) applies the selection through the native gather
+    kernels. Contract in include/otbx.h (otbx_filter_sel)."""
+
+    def __init__(self, clauses, count_only=False, n=None):
+        super().__init__()
+        self.clauses = [list(c) for c in clauses]
+        terms = [t for c in self.clauses for t in c]
+        if any(len(c) == 0 for c in self.clauses):
+            raise OtbxError(3, "filter: an empty clause is FALSE for every "
+                               "row — drop the scan instead")
+        if len(terms) > MAX_QUAL_TERMS:
+            raise OtbxError(3, f"filter: at most {MAX_QUAL_TERMS} terms")
+        for t in terms:
+            if not isinstance(t, QualTerm):
+                raise OtbxError(3, "filter: build terms with qual_term()")
+        if n is None:
+            if not terms:
+                raise OtbxError(3, "filter: no qual — pass n")
+            n = len(terms[0].col)
+        self.n = int(n)
+        for t in terms:
+            if len(t.col) != self.n:
+                raise OtbxError(3, "filter: columns differ in length")
+        self.count_only = bool(count_only)
+        self.sel = None
+        self.count = None
+        self.filter_ms = None
+
+    def qual(self):
+        """The otbx_qual handed to otbx_filter_sel."""
+        q = QualDev()
+        i = 0
+        for cid, clause in enumerate(self.clauses):
+            for t in clause:
+                d = q.term[i]
+                d.col = t.col.data_ptr()
+                d.nulls = t.nulls.data_ptr() if t.nulls is not None else None
+                d.type = _SORT_TYPE[t.col.dtype]
+                d.op = CMP_OPS[t.op]
+                d.clause = cid
+                if isinstance(t.rhs, torch.Tensor):
+                    d.rcol = t.rhs.data_ptr()
+                    d.rnulls = t.rnulls.data_ptr() \
+                        if t.rnulls is not None else None
+                elif t.rhs is not None:
+                    if t.col.dtype == torch.float64:
+                        d.cf = float(t.rhs)
+                    else:
+                        d.ci = t.rhs
+                i += 1
+        q.nterms = i
+        return q
+
+    def _run(self):
+        L = lib()
+        n = self.n
+        ws_bytes = C.c_size_t(0)
+        check(L.otbx_filter_workspace_bytes(C.c_int64(n), C.byref(ws_bytes)),
+              "otbx_filter_workspace_bytes")
+        ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8,
+                         device="cuda")
+        sel = None if self.count_only else \
+            torch.empty(max(n, 1), dtype=torch.int64, device="cuda")
+        nsel = torch.zeros(1, dtype=torch.int64, device="cuda")
+        q = self.qual()
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        call("otbx_filter_sel", C.byref(q), C.c_int64(n),
+             C.c_void_p(ws.data_ptr()), C.c_size_t(ws_bytes.value),
+             C.c_void_p(sel.data_ptr()) if sel is not None else None,
+             C.c_void_p(nsel.data_ptr()), _stream())
+        ev1.record()
+        self.count = int(nsel.cpu().item())
+        self.filter_ms = ev0.elapsed_time(ev1)
+        if self.count_only:
+            return [(self.count,)]
+        self.sel = sel[:self.count]
+        return [self.sel]
+
+    def gather(self, col):
+        """The passing rows of col (runs the node if it has not run)."""
+        if self.count_only:
+            raise OtbxError(3, "filter: count_only keeps no selection")
+        if self.sel is None:
+            self._run()
+        return gather(col, self.sel)
+
+    def explain(self):
+        if self.filter_ms is None:
+            return None
+        return {"filter": self.filter_ms}
 
 
 class GpuHashAgg(CustomScanState):

@@ -15,6 +15,11 @@ distinct from the fused query pipelines.
                                    from its sort, next to a plain-torch
                                    composition of the ranking functions
                                    (writes profiles/window_ops.txt, or PATH)
+  generic_ops_bench.py --filter [--out PATH]
+                                   otbx_filter_sel at 600 M rows next to
+                                   otbx_scan_count and to a plain-torch
+                                   composition of the same quals (writes
+                                   profiles/filter_ops.txt, or PATH)
 """
 import ctypes as C
 import os
@@ -503,8 +508,175 @@ def bench_window(out_path):
         f.write("\n".join(lines) + "\n")
 
 
+class _FilterCall:
+    """otbx_filter_sel with everything preallocated; clauses as GpuFilter
+    takes them"""
+
+    def __init__(self, clauses, count_only=False):
+        self.node = ex.GpuFilter(clauses, count_only=count_only)
+        self.n = self.node.n
+        wsb = C.c_size_t(0)
+        lib().otbx_filter_workspace_bytes(C.c_int64(self.n), C.byref(wsb))
+        self.wsb = wsb.value
+        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device="cuda")
+        self.sel = None if count_only else \
+            torch.empty(self.n, dtype=torch.int64, device="cuda")
+        self.nsel = torch.zeros(1, dtype=torch.int64, device="cuda")
+        self.qual = self.node.qual()
+        self.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        # bytes of the columns and masks the qual references, each once
+        seen = {}
+        for c in clauses:
+            for t in c:
+                for x in (t.col, t.nulls, t.rnulls,
+                          t.rhs if isinstance(t.rhs, torch.Tensor) else None):
+                    if x is not None:
+                        seen[x.data_ptr()] = x.element_size()
+        self.col_bytes = sum(seen.values())
+
+    def __call__(self):
+        call("otbx_filter_sel", C.byref(self.qual), C.c_int64(self.n),
+             C.c_void_p(self.ws.data_ptr()), C.c_size_t(self.wsb),
+             C.c_void_p(self.sel.data_ptr()) if self.sel is not None else None,
+             C.c_void_p(self.nsel.data_ptr()), self.stream)
+
+    def count(self):
+        return int(self.nsel.item())
+
+    def bytes_per_row(self):
+        """referenced columns; when the selection is written also the
+        bitmask (written and read back) and 8 B per selected row"""
+        if self.sel is None:
+            return self.col_bytes
+        return self.col_bytes + 2 / 8 + 8 * self.count() / self.n
+
+
+def bench_filter(out_path):
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    say("# tools/generic_ops_bench.py --filter — best / worst of 5 wall time "
+        "after torch.cuda.synchronize(), columns staged, workspace and "
+        "selection preallocated")
+    say("# algorithmic B/row = referenced columns and masks [+ 2/8 (bitmask "
+        "written and read back) + 8 x selectivity when the selection is "
+        "written]")
+    g = torch.Generator(device="cuda").manual_seed(13)
+    n = 600_000_000
+    date = torch.randint(0, 2500, (n,), dtype=torch.int32, device="cuda",
+                         generator=g)
+    price = torch.rand(n, dtype=torch.float64, device="cuda", generator=g)
+    pnull = (torch.rand(n, device="cuda", generator=g) < 0.05).to(torch.uint8)
+    flag = torch.randint(0, 25, (n,), dtype=torch.uint8, device="cuda",
+                         generator=g)
+    rare = torch.randint(0, 10_000, (n,), dtype=torch.int32, device="cuda",
+                         generator=g)
+    T = ex.qual_term
+
+    def report(tag, what, fc, torch_fn, extra=""):
+        fb, fw = _best_of_5(fc)
+        cnt = fc.count()
+        bpr = fc.bytes_per_row()
+        tbs = n * bpr / fb / 1e12
+        say(f"({tag}) n={n:_} {what}: otbx_filter_sel best {fb*1e3:8.3f} ms  "
+            f"worst {fw*1e3:8.3f} ms (spread {(fw-fb)/fb*100:.1f} %)  "
+            f"selected {cnt:_} ({cnt/n*100:.4f} %)  {bpr:.2f} B/row "
+            f"algorithmic = {n*bpr/1e9:.2f} GB  {tbs:5.2f} TB/s = "
+            f"{tbs*1e12/COPY_CEILING*100:4.1f} % of the 6.29 TB/s copy "
+            f"ceiling{extra}")
+        tb, tw = _best_of_5(torch_fn)
+        ref = torch_fn()
+        if fc.sel is None:
+            same = int(ref.item()) == cnt
+        else:
+            same = len(ref) == cnt and bool(torch.equal(ref, fc.sel[:cnt]))
+        say(f"    plain torch on the same columns: best {tb*1e3:8.3f} ms  "
+            f"worst {tw*1e3:8.3f} ms; torch / otbx_filter_sel time ratio: "
+            f"{tb/fb:.2f}; same result: {same}")
+        assert same, f"case ({tag}): torch and otbx_filter_sel disagree"
+        del ref
+        torch.cuda.empty_cache()
+        return fb, fw
+
+    # (a) Q1-shaped count: date <= c, next to the specialised otbx_scan_count
+    c98, c01 = 2449, 24
+    out = torch.zeros(1, dtype=torch.int64, device="cuda")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def scan_count():
+        call("otbx_scan_count", C.c_void_p(date.data_ptr()), C.c_int64(n),
+             C.c_int32(c98), C.c_void_p(out.data_ptr()), stream)
+
+    sb, sw = _best_of_5(scan_count)
+    say(f"(a) yardstick otbx_scan_count (date <= {c98}, 4 B/row): best "
+        f"{sb*1e3:8.3f} ms  worst {sw*1e3:8.3f} ms (spread "
+        f"{(sw-sb)/sb*100:.1f} %)  {n*4/sb/1e12:5.2f} TB/s = "
+        f"{n*4/sb/COPY_CEILING*100:4.1f} % of the ceiling; count "
+        f"{int(out.item()):_}")
+    fc = _FilterCall([[T(date, "<=", c98)]], count_only=True)
+    fb, fw = report("a", f"date <= {c98}, count only", fc,
+                    lambda: (date <= c98).sum())
+    assert fc.count() == int(out.item())
+    say(f"    otbx_filter_sel / otbx_scan_count time ratio: {fb/sb:.2f} "
+        f"(best / best; difference {(fb-sb)*1e3:+.3f} ms, spreads "
+        f"{(fw-fb)*1e3:.3f} ms and {(sw-sb)*1e3:.3f} ms)")
+    del fc
+
+    # (b) the same qual with the selection written
+    for c in (c98, c01):
+        fc = _FilterCall([[T(date, "<=", c)]])
+        report("b", f"date <= {c}, selection written", fc,
+               lambda: (date <= c).nonzero().squeeze(1))
+        del fc
+        torch.cuda.empty_cache()
+
+    # (c) four columns: i32, nullable f64, u8 twice in an OR
+    def torch_c():
+        return ((date <= c98) & (price < 0.5) & (pnull == 0) &
+                ((flag == 3) | (flag == 7))).nonzero().squeeze(1)
+
+    fc = _FilterCall([[T(date, "<=", c98)], [T(price, "<", 0.5, nulls=pnull)],
+                      [T(flag, "=", 3), T(flag, "=", 7)]])
+    report("c", f"date <= {c98} AND price < 0.5 (nullable) AND (flag = 3 OR "
+           "flag = 7)", fc, torch_c)
+    del fc
+    torch.cuda.empty_cache()
+
+    # (d) a 1-in-10^4 clause first: waves without a survivor skip the loads
+    # of the later clauses; the same qual with that clause last reads all
+    def torch_d():
+        return ((rare == 0) & (price < 0.5) & (pnull == 0) &
+                ((flag == 3) | (flag == 7))).nonzero().squeeze(1)
+
+    lead = [[T(rare, "=", 0)], [T(price, "<", 0.5, nulls=pnull)],
+            [T(flag, "=", 3), T(flag, "=", 7)]]
+    fc = _FilterCall(lead)
+    db, _ = report("d", "rare = 0 (1 in 10^4) AND price < 0.5 (nullable) AND "
+                   "(flag = 3 OR flag = 7), selective clause FIRST", fc,
+                   torch_d, extra=" (nominal: B/row counts every column)")
+    del fc
+    torch.cuda.empty_cache()
+    fc = _FilterCall(lead[1:] + lead[:1])
+    lb, _ = report("d", "the same qual, selective clause LAST", fc, torch_d)
+    say(f"    clause order: last / first time ratio {lb/db:.2f}")
+    del fc
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
     ex.init_device(0)
+    if "--filter" in sys.argv:
+        repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        out_path = os.path.join(repo, "profiles", "filter_ops.txt")
+        if "--out" in sys.argv:
+            out_path = sys.argv[sys.argv.index("--out") + 1]
+        bench_filter(out_path)
+        sys.exit(0)
     if "--window" in sys.argv:
         repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         out_path = os.path.join(repo, "profiles", "window_ops.txt")
