@@ -46,7 +46,12 @@
  *                            typed, nullable comparisons (execScan.c:140,
  *                            EEOP_QUAL execExprInterp.c:919) → the ordered
  *                            selection vector the other operators gather by
- *   merge (Coordinator)    — NOT here: the shard merge (execFragment.c:3877)
+ *   otbx_project           — ExecProject for one target-list expression:
+ *                            typed arithmetic, casts, comparisons, Kleene
+ *                            logic, CASE and COALESCE (execExprInterp.c)
+ *                            over selected rows, with the reference's
+ *                            first-error behaviour in a device error slot
+ *   merge (Coordinator)   — NOT here: the shard merge (execFragment.c:3877)
  *                            is a collective over ranks, done by the host
  *                            layer with RCCL (torch.distributed) on the
  *                            partial-state buffers these calls return.
@@ -720,6 +725,134 @@ otbx_status otbx_filter_sel(const otbx_qual *q, int64_t n,
                             int64_t *sel_dev,   /* cap n; NULL = count only */
                             int64_t *nsel_dev,  /* int64[1], required       */
                             void *stream);
+
+/* ---- generic GPU Project: one typed scalar expression per row ----
+ * The ExecProject analog for one target-list entry (the expression steps of
+ * executor/execExprInterp.c): a postfix program over typed, nullable
+ * columns is evaluated for every output row into one output column plus
+ * null mask. With sel_dev the rows are read through a selection vector
+ * (what otbx_filter_sel wrote): output row j is computed from source row
+ * sel_dev[j]; rows the selection leaves out are never evaluated. An entry
+ * outside [0, n_src) is clamped into it, so a broken selection can never
+ * index outside the columns.
+ *
+ * PROGRAM: instr[0 .. ninstr) in postfix order over a value stack of at
+ * most OTBX_MAX_EXPR_DEPTH entries. A value is INT8 (int64), FLOAT8
+ * (double) or BOOL and carries a null flag. I32 and U8 columns widen to
+ * INT8 on load (the int48 implicit cast); int4-typed arithmetic does not
+ * exist here. Every function is strict (a NULL operand gives NULL, the
+ * function is not called) unless stated:
+ *   COL              push column `col` of `type` OTBX_SORT_*, mask `nulls`
+ *   CONST            push `ci` (INT8; BOOL: nonzero = TRUE) or `cf` (FLOAT8)
+ *                    of `type` OTBX_EXT_*; isnull != 0: the NULL of that type
+ *   ADD SUB MUL DIV  two INT8 (int8pl/mi/mul/div, utils/adt/int8.c:534-640)
+ *                    or two FLOAT8 (float8pl/mi/mul/div, float.c:809-1025)
+ *   MOD              two INT8 (int8mod :643): x % -1 = 0, sign of dividend
+ *   NEG ABS          one INT8 (int8um, int8abs) or FLOAT8 (sign bit only)
+ *   CAST             `type` = OTBX_EXT_FLOAT8 on INT8: i8tod (int8.c:1235);
+ *                    OTBX_EXT_INT8 on FLOAT8: dtoi8 (:1249), rint (ties to
+ *                    even) then the range check
+ *   EQ NE LT LE GT GE  two INT8 or two FLOAT8 → BOOL; FLOAT8 compares as
+ *                    float8_cmp_internal, exactly as the Filter and the Sort
+ *                    do: every NaN equals every NaN and is above +Inf,
+ *                    -0 = +0
+ *   AND OR           two BOOL, Kleene (EEOP_BOOL_AND_STEP* / OR_STEP*,
+ *                    execExprInterp.c:783-904); not strict
+ *   NOT              one BOOL
+ *   ISNULL NOTNULL   any type → BOOL, never NULL
+ *   CASE             pops else, then, cond: `then` iff cond is TRUE, a NULL
+ *                    cond takes the else arm (EEOP_JUMP_IF_NOT_TRUE :964);
+ *                    arms of one type
+ *   COALESCE         two values of one type: the first if non-NULL, else
+ *                    the second
+ *
+ * ERRORS are values. The reference aborts at the first row whose evaluation
+ * raises and never evaluates the untaken arm of a CASE, the right side of an
+ * AND whose left is FALSE (OR: TRUE) or the second argument of a COALESCE
+ * whose first is non-NULL. Evaluation here is eager and every stack value
+ * carries an error code:
+ *   - strict operator: its first operand's code if nonzero, else the
+ *     second's, else — only when every operand is non-NULL — its own. A NULL
+ *     operand never hides an error raised in a sibling subtree.
+ *   - CASE: cond's code, else the code of the chosen arm only.
+ *   - AND / OR: the left code; the right code only if the left value did
+ *     not decide the result. COALESCE: the first code; the second only if
+ *     the first value is NULL. ISNULL / NOTNULL: the operand's code.
+ *   - the value stored under a NULL is never used and never raises.
+ * Codes (OTBX_EXERR_*): 1 division by zero (INT8 x / 0, x % 0; FLOAT8
+ * x / ±0.0 whatever x, NaN and 0 included); 2 bigint out of range (INT8
+ * overflow of + - *, INT64_MIN / -1, -INT64_MIN, abs(INT64_MIN); dtoi8 of
+ * NaN or of a rounded value outside [-2^63, 2^63) — the reference's check
+ * lets exactly 2^63 through into an undefined C conversion, here 2^63
+ * raises); 3 value out of range: overflow (CHECKFLOATVAL, float.c:58:
+ * FLOAT8 result ±Inf and no operand was); 4 value out of range: underflow
+ * (result 0 and MUL: neither operand 0, DIV: dividend not 0; ADD / SUB
+ * never); 5 integer out of range (int84, int8.c:1201, on an I32 output).
+ *
+ * ERROR SLOT: *err_dev receives -1 when no output row raised, otherwise
+ * (j << 8) | code for the SMALLEST output position j that raised and that
+ * row's code (deterministic: an unsigned 64-bit minimum). It is written by
+ * the call, stream-ordered. When the slot is not -1 the contents of out_dev
+ * and out_null_dev are unspecified: the caller MUST read the slot before it
+ * uses the output.
+ *
+ * OUTPUT: out_type OTBX_SORT_I64 takes an INT8 result, F64 a FLOAT8 one,
+ * I32 an INT8 one through int84's range check (code 5), U8 a BOOL as 0 / 1.
+ * out_null_dev[j] is 1 where the result is NULL, else 0; the value stored
+ * under a NULL is 0. out_null_dev may be NULL only when the program cannot
+ * produce NULL, decided by the abstract interpretation that type-checks it:
+ * a COL with a mask and a NULL CONST are the only sources; arithmetic,
+ * casts, comparisons, NOT, AND, OR and CASE are nullable when any value
+ * operand is (CASE: either arm), COALESCE when both are, ISNULL / NOTNULL
+ * never. FLOAT8 results are bit-exact IEEE (no contraction).
+ *
+ * Columns, masks and outputs need only the natural alignment of their
+ * element type (col[1:] is legal); 16-byte-aligned ones take the
+ * vector-access path on whole tiles. No workspace, nothing cached, no host
+ * synchronisation. Checked before any HIP call, each returning
+ * OTBX_ERR_INVALID: e or err_dev NULL; ninstr outside 1..32; an unknown op
+ * or type code; a stack underflow or a depth above 8; operand types that do
+ * not fit the operator (INT8 meeting FLOAT8 without a cast, MOD on FLOAT8,
+ * AND on a non-BOOL, CASE arms of different types, a CAST to the operand's
+ * own type or from / to BOOL, ...); a final stack that does not hold exactly
+ * one value; out_type not matching it; n < 0, n > INT32_MAX, n_src < 0,
+ * n > n_src without sel_dev, n > 0 with n_src == 0; a NULL col with n > 0;
+ * out_dev NULL with n > 0; out_null_dev NULL although the result is
+ * nullable. n == 0 is valid and writes *err_dev = -1.
+ * sizeof(otbx_exprinstr) == 48, sizeof(otbx_expr) == 1544. */
+enum { OTBX_EX_COL = 0, OTBX_EX_CONST, OTBX_EX_ADD, OTBX_EX_SUB, OTBX_EX_MUL,
+       OTBX_EX_DIV, OTBX_EX_MOD, OTBX_EX_NEG, OTBX_EX_ABS, OTBX_EX_CAST,
+       OTBX_EX_EQ, OTBX_EX_NE, OTBX_EX_LT, OTBX_EX_LE, OTBX_EX_GT, OTBX_EX_GE,
+       OTBX_EX_AND, OTBX_EX_OR, OTBX_EX_NOT, OTBX_EX_ISNULL, OTBX_EX_NOTNULL,
+       OTBX_EX_CASE, OTBX_EX_COALESCE };
+enum { OTBX_EXT_INT8 = 0, OTBX_EXT_FLOAT8 = 1, OTBX_EXT_BOOL = 2 };
+enum { OTBX_EXERR_DIV0 = 1, OTBX_EXERR_INT8 = 2, OTBX_EXERR_OVERFLOW = 3,
+       OTBX_EXERR_UNDERFLOW = 4, OTBX_EXERR_INT4 = 5 };
+#define OTBX_MAX_EXPR_INSTRS 32
+#define OTBX_MAX_EXPR_DEPTH  8
+typedef struct {
+    const void    *col;     /* COL: device column of `type`                   */
+    const uint8_t *nulls;   /* COL: byte per row, nonzero = NULL; may be NULL */
+    int64_t        ci;      /* CONST INT8 / BOOL payload                      */
+    double         cf;      /* CONST FLOAT8 payload                           */
+    int32_t        op;      /* OTBX_EX_*                                      */
+    int32_t        type;    /* COL: OTBX_SORT_*; CONST / CAST: OTBX_EXT_*     */
+    int32_t        isnull;  /* CONST: nonzero = the NULL of `type`            */
+    int32_t        _pad;
+} otbx_exprinstr;
+typedef struct {
+    int32_t ninstr; int32_t _pad;
+    otbx_exprinstr instr[OTBX_MAX_EXPR_INSTRS];
+} otbx_expr;
+
+otbx_status otbx_project(const otbx_expr *e,
+                         const int64_t *sel_dev,  /* NULL = identity          */
+                         int64_t n,      /* output rows (= len(sel) if given) */
+                         int64_t n_src,  /* rows in the columns               */
+                         int32_t out_type,        /* OTBX_SORT_*              */
+                         void *out_dev, uint8_t *out_null_dev,
+                         int64_t *err_dev,        /* int64[1], required       */
+                         void *stream);
 
 /* ---- repartition exchange ----
  * The GPU half of the reference's "Distribute results by H: col" exchange

@@ -99,6 +99,20 @@ class QualDev(C.Structure):
     _fields_ = [("nterms", C.c_int32), ("term", QualTermDev * 16)]
 
 
+class ExprInstrDev(C.Structure):
+    """otbx_exprinstr (include/otbx.h): one postfix instruction, 48 bytes."""
+    _fields_ = [("col", C.c_void_p), ("nulls", C.c_void_p),
+                ("ci", C.c_int64), ("cf", C.c_double),
+                ("op", C.c_int32), ("type", C.c_int32),
+                ("isnull", C.c_int32), ("_pad", C.c_int32)]
+
+
+class ExprDev(C.Structure):
+    """otbx_expr: a postfix program of up to 32 instructions, 1544 bytes."""
+    _fields_ = [("ninstr", C.c_int32), ("_pad", C.c_int32),
+                ("instr", ExprInstrDev * 32)]
+
+
 class PartDev(C.Structure):
     _fields_ = [
         ("n", C.c_int64),
@@ -172,4 +186,5 @@ EXPORTED_SYMBOLS = [
     "otbx_sort_workspace_bytes", "otbx_sort_perm",
     "otbx_window_workspace_bytes", "otbx_window",
     "otbx_filter_workspace_bytes", "otbx_filter_sel",
+    "otbx_project",
 ]

@@ -16,7 +16,7 @@ import math
 
 import torch
 
-from ._lib import (CustomerDev, KeysetDev, LineitemDev, OrdersDev,
+from ._lib import (CustomerDev, ExprDev, KeysetDev, LineitemDev, OrdersDev,
                    OtbxError, PartDev, QualDev, SortSpecDev, WindowOutDev,
                    call, check, lib)
 
@@ -956,6 +956,349 @@ class GpuFilter(CustomScanState):
         if self.filter_ms is None:
             return None
         return {"filter": self.filter_ms}
+
+
+# ---------------- Project: typed scalar expressions ----------------
+
+EX_OPS = {"col": 0, "const": 1, "+": 2, "-": 3, "*": 4, "/": 5, "%": 6,
+          "neg": 7, "abs": 8, "cast": 9, "=": 10, "<>": 11, "<": 12,
+          "<=": 13, ">": 14, ">=": 15, "and": 16, "or": 17, "not": 18,
+          "isnull": 19, "notnull": 20, "case": 21,
+          "coalesce": 22}                         # OTBX_EX_*
+EX_TYPES = {"i64": 0, "f64": 1, "bool": 2}        # OTBX_EXT_*
+MAX_EXPR_INSTRS = 32                              # OTBX_MAX_EXPR_INSTRS
+MAX_EXPR_DEPTH = 8                                # OTBX_MAX_EXPR_DEPTH
+PROJECT_TILE = 1024                               # rows per workgroup
+PROJECT_ERRORS = {1: "division by zero", 2: "bigint out of range",
+                  3: "value out of range: overflow",
+                  4: "value out of range: underflow",
+                  5: "integer out of range"}      # OTBX_EXERR_*
+_EX_OUT_DTYPE = {"i64": torch.int64, "f64": torch.float64,
+                 "bool": torch.uint8}
+
+
+class Expr:
+    """A typed scalar expression tree for GpuProject; build it with col(),
+    const(), null(), case(), coalesce() and the operators below. vtype is
+    "i64", "f64" or "bool"; nullable follows the rules of include/otbx.h.
+    Where an i64 operand meets an f64 one the i64 side is cast (i8tod), as
+    the reference's parser picks the float8 operator. `==` is NOT
+    overloaded: use .eq()."""
+    __slots__ = ("op", "args", "vtype", "nullable", "payload", "nulls",
+                 "ninstr", "depth", "n_src")
+
+    def __init__(self, op, args, vtype, nullable, payload=None, nulls=None,
+                 n_src=None):
+        self.op, self.args, self.vtype = op, tuple(args), vtype
+        self.nullable, self.payload, self.nulls = nullable, payload, nulls
+        self.ninstr = 1 + sum(a.ninstr for a in self.args)
+        self.depth = max([1] + [i + a.depth for i, a in enumerate(self.args)])
+        for a in self.args:
+            if a.n_src is not None:
+                if n_src is not None and a.n_src != n_src:
+                    raise OtbxError(3, "project: columns differ in length")
+                n_src = a.n_src
+        self.n_src = n_src
+        if self.ninstr > MAX_EXPR_INSTRS:
+            raise OtbxError(3, "project: the expression needs more than "
+                               f"{MAX_EXPR_INSTRS} instructions")
+        if self.depth > MAX_EXPR_DEPTH:
+            raise OtbxError(3, "project: the expression needs a stack deeper "
+                               f"than {MAX_EXPR_DEPTH}")
+
+    # ---- arithmetic ----
+    def _arith(self, op, other, swap=False):
+        a, b = _ex_unify(self, other, "project: " + op)
+        if swap:
+            a, b = b, a
+        if a.vtype == "bool" or (op == "%" and a.vtype != "i64"):
+            raise OtbxError(3, f"project: {op} on {a.vtype} operands")
+        return Expr(op, (a, b), a.vtype, a.nullable or b.nullable)
+
+    def __add__(self, o): return self._arith("+", o)
+    def __radd__(self, o): return self._arith("+", o, True)
+    def __sub__(self, o): return self._arith("-", o)
+    def __rsub__(self, o): return self._arith("-", o, True)
+    def __mul__(self, o): return self._arith("*", o)
+    def __rmul__(self, o): return self._arith("*", o, True)
+    def __truediv__(self, o): return self._arith("/", o)
+    def __rtruediv__(self, o): return self._arith("/", o, True)
+    def __mod__(self, o): return self._arith("%", o)
+    def __rmod__(self, o): return self._arith("%", o, True)
+
+    def _unary(self, op):
+        if self.vtype == "bool":
+            raise OtbxError(3, f"project: {op} on a bool operand")
+        return Expr(op, (self,), self.vtype, self.nullable)
+
+    def __neg__(self): return self._unary("neg")
+    def __abs__(self): return self._unary("abs")
+
+    def cast(self, to):
+        """i8tod ("f64") on an i64 value, dtoi8 ("i64") on an f64 one."""
+        if to not in ("i64", "f64"):
+            raise OtbxError(3, f"project: cast to {to!r}")
+        if self.vtype == "bool" or self.vtype == to:
+            raise OtbxError(3, f"project: cast of {self.vtype} to {to}")
+        return Expr("cast", (self,), to, self.nullable, payload=to)
+
+    # ---- comparisons ----
+    def _cmp(self, op, other):
+        a, b = _ex_unify(self, other, "project: " + op)
+        if a.vtype == "bool":
+            raise OtbxError(3, f"project: {op} on bool operands")
+        return Expr(op, (a, b), "bool", a.nullable or b.nullable)
+
+    def eq(self, o): return self._cmp("=", o)
+    def ne(self, o): return self._cmp("<>", o)
+    def lt(self, o): return self._cmp("<", o)
+    def le(self, o): return self._cmp("<=", o)
+    def gt(self, o): return self._cmp(">", o)
+    def ge(self, o): return self._cmp(">=", o)
+
+    # ---- boolean ----
+    def _bool2(self, op, other, swap=False):
+        a, b = self, _ex_lift(other)
+        if swap:
+            a, b = b, a
+        if a.vtype != "bool" or b.vtype != "bool":
+            raise OtbxError(3, f"project: {op} needs bool operands")
+        return Expr(op, (a, b), "bool", a.nullable or b.nullable)
+
+    def __and__(self, o): return self._bool2("and", o)
+    def __rand__(self, o): return self._bool2("and", o, True)
+    def __or__(self, o): return self._bool2("or", o)
+    def __ror__(self, o): return self._bool2("or", o, True)
+
+    def __invert__(self):
+        if self.vtype != "bool":
+            raise OtbxError(3, "project: not needs a bool operand")
+        return Expr("not", (self,), "bool", self.nullable)
+
+    def isnull(self): return Expr("isnull", (self,), "bool", False)
+    def notnull(self): return Expr("notnull", (self,), "bool", False)
+
+    def __bool__(self):
+        raise OtbxError(3, "project: an expression has no truth value — "
+                           "combine with & | ~ and compare with .eq()")
+
+    # ---- lowering ----
+    def program(self):
+        """The postfix instruction list: (op,) tuples, leaves and casts with
+        their payload — ("col", tensor, nulls), ("const", vtype, value) with
+        value None for the NULL constant, ("cast", vtype)."""
+        out = []
+        for a in self.args:
+            out.extend(a.program())
+        if self.op == "col":
+            out.append(("col", self.payload, self.nulls))
+        elif self.op == "const":
+            out.append(("const", self.vtype, self.payload))
+        elif self.op == "cast":
+            out.append(("cast", self.vtype))
+        else:
+            out.append((self.op,))
+        return out
+
+    def to_dev(self):
+        """The otbx_expr handed to otbx_project."""
+        return program_to_dev(self.program())
+
+
+def program_to_dev(program):
+    """otbx_expr from an instruction list in Expr.program()'s form."""
+    e = ExprDev()
+    if len(program) > MAX_EXPR_INSTRS:
+        raise OtbxError(3, f"project: more than {MAX_EXPR_INSTRS} instructions")
+    for i, ins in enumerate(program):
+        d = e.instr[i]
+        d.op = EX_OPS[ins[0]]
+        if ins[0] == "col":
+            d.type = _SORT_TYPE[ins[1].dtype]
+            d.col = ins[1].data_ptr()
+            d.nulls = ins[2].data_ptr() if ins[2] is not None else None
+        elif ins[0] == "const":
+            d.type = EX_TYPES[ins[1]]
+            if ins[2] is None:
+                d.isnull = 1
+            elif ins[1] == "f64":
+                d.cf = ins[2]
+            else:
+                d.ci = int(ins[2])
+        elif ins[0] == "cast":
+            d.type = EX_TYPES[ins[1]]
+    e.ninstr = len(program)
+    return e
+
+
+def _ex_lift(x):
+    if isinstance(x, Expr):
+        return x
+    return const(x)
+
+
+def _ex_unify(a, b, what):
+    """Both operands as Expr of one numeric type: Python numbers lift to
+    constants (an int beside an f64 operand to an f64 constant), and an i64
+    operand beside an f64 one is cast."""
+    if not isinstance(a, Expr) and isinstance(b, Expr) and \
+            b.vtype == "f64" and isinstance(a, int) and not isinstance(a, bool):
+        a = float(a)
+    if not isinstance(b, Expr) and isinstance(a, Expr) and \
+            a.vtype == "f64" and isinstance(b, int) and not isinstance(b, bool):
+        b = float(b)
+    a, b = _ex_lift(a), _ex_lift(b)
+    if a.vtype != b.vtype:
+        if {a.vtype, b.vtype} != {"i64", "f64"}:
+            raise OtbxError(3, f"{what}: {a.vtype} with {b.vtype}")
+        if a.vtype == "i64":
+            a = a.cast("f64")
+        else:
+            b = b.cast("f64")
+    return a, b
+
+
+def col(tensor, nulls=None):
+    """A column leaf: a device tensor of dtype int64, float64, int32 or uint8
+    (the two narrow ones widen to i64) with an optional uint8 null mask."""
+    if not isinstance(tensor, torch.Tensor) or tensor.dtype not in _SORT_TYPE \
+            or tensor.dim() != 1:
+        raise OtbxError(3, "project: unsupported column "
+                           f"{getattr(tensor, 'dtype', type(tensor))}")
+    if nulls is not None and (not isinstance(nulls, torch.Tensor) or
+                              nulls.dtype != torch.uint8 or
+                              nulls.shape != tensor.shape):
+        raise OtbxError(3, "project: a null mask is a uint8 tensor of the "
+                           "column's length")
+    return Expr("col", (), "f64" if tensor.dtype == torch.float64 else "i64",
+                nulls is not None, payload=tensor, nulls=nulls,
+                n_src=len(tensor))
+
+
+def const(v):
+    """A constant: bool → bool, int → i64, float → f64."""
+    if isinstance(v, bool):
+        return Expr("const", (), "bool", False, payload=v)
+    if isinstance(v, int):
+        if not -2**63 <= v < 2**63:
+            raise OtbxError(3, "project: constant outside int64")
+        return Expr("const", (), "i64", False, payload=v)
+    if isinstance(v, float):
+        return Expr("const", (), "f64", False, payload=v)
+    raise OtbxError(3, f"project: no constant from {type(v).__name__}")
+
+
+def null(vtype):
+    """The NULL constant of type "i64", "f64" or "bool"."""
+    if vtype not in EX_TYPES:
+        raise OtbxError(3, f"project: unknown type {vtype!r}")
+    return Expr("const", (), vtype, True, payload=None)
+
+
+def case(cond, then, else_):
+    """CASE WHEN cond THEN then ELSE else_ END; nest it for more arms."""
+    cond = _ex_lift(cond)
+    if cond.vtype != "bool":
+        raise OtbxError(3, "project: CASE needs a bool condition")
+    if isinstance(then, Expr) or isinstance(else_, Expr):
+        t, f = _ex_unify(then, else_, "project: CASE arms")
+    else:
+        t, f = _ex_unify(_ex_lift(then), else_, "project: CASE arms")
+    return Expr("case", (cond, t, f), t.vtype, t.nullable or f.nullable)
+
+
+def coalesce(a, b):
+    """The first operand if it is non-NULL, else the second."""
+    if isinstance(a, Expr) or isinstance(b, Expr):
+        a, b = _ex_unify(a, b, "project: COALESCE")
+    else:
+        a, b = _ex_unify(_ex_lift(a), b, "project: COALESCE")
+    return Expr("coalesce", (a, b), a.vtype, a.nullable and b.nullable)
+
+
+class GpuProject(CustomScanState):
+    """One target-list expression for any plan shape (ExecProject over the
+    expression interpreter, execExprInterp.c): evaluates `expr` for every
+    row — with `sel`, the int64 selection GpuFilter yielded, only for the
+    selected rows, read through it — into a new column. Yields ONE tuple
+    (values, nulls): device tensors of n rows, nulls a uint8 mask or None
+    when the expression cannot be NULL. They go unchanged into GpuHashAgg
+    (vals / val_null), GpuSort and qual_term. `out`: an optional
+    preallocated result tensor; an int32 one takes an i64 result through the
+    int84 range check. `n`: the row count of an expression without columns.
+    An error the reference would have raised (division by zero, bigint out
+    of range, float8 overflow / underflow, integer out of range) is raised
+    after the run as OtbxError(4) naming the first raising output row.
+    Contract in include/otbx.h (otbx_project)."""
+
+    def __init__(self, expr, sel=None, n=None, out=None):
+        super().__init__()
+        if not isinstance(expr, Expr):
+            raise OtbxError(3, "project: build the expression with col(), "
+                               "const(), ...")
+        self.expr = expr
+        if sel is not None and (not isinstance(sel, torch.Tensor) or
+                                sel.dtype != torch.int64 or sel.dim() != 1):
+            raise OtbxError(3, "project: sel is an int64 tensor of row ids")
+        self.sel = sel
+        if n is None:
+            if sel is not None:
+                n = len(sel)
+            elif expr.n_src is not None:
+                n = expr.n_src
+            else:
+                raise OtbxError(3, "project: no column — pass n")
+        self.n = int(n)
+        self.n_src = expr.n_src if expr.n_src is not None else self.n
+        if self.n < 0 or (sel is not None and self.n > len(sel)) or \
+                (sel is None and self.n > self.n_src) or \
+                (self.n > 0 and self.n_src == 0):
+            raise OtbxError(3, "project: n outside the input")
+        want = _EX_OUT_DTYPE[expr.vtype]
+        if out is not None:
+            ok = isinstance(out, torch.Tensor) and out.dim() == 1 and \
+                len(out) == self.n and \
+                (out.dtype == want or
+                 (out.dtype == torch.int32 and expr.vtype == "i64"))
+            if not ok:
+                raise OtbxError(3, f"project: out is a {want} tensor of n rows")
+        self.out = out
+        self.project_ms = None
+        self.err = None
+
+    def _run(self):
+        n = self.n
+        # an empty tensor has no address: with n == 0 the mask the call is
+        # handed is one spare byte, and out (never written) stays NULL
+        out = self.out if self.out is not None else \
+            torch.empty(n, dtype=_EX_OUT_DTYPE[self.expr.vtype], device="cuda")
+        nbuf = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda") \
+            if self.expr.nullable else None
+        nulls = nbuf[:n] if nbuf is not None else None
+        err = torch.empty(1, dtype=torch.int64, device="cuda")
+        e = self.expr.to_dev()
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        call("otbx_project", C.byref(e),
+             C.c_void_p(self.sel.data_ptr()) if self.sel is not None else None,
+             C.c_int64(n), C.c_int64(self.n_src),
+             C.c_int32(_SORT_TYPE[out.dtype]),
+             C.c_void_p(out.data_ptr()) if n > 0 else None,
+             C.c_void_p(nbuf.data_ptr()) if nbuf is not None else None,
+             C.c_void_p(err.data_ptr()), _stream())
+        ev1.record()
+        self.err = int(err.cpu().item())
+        self.project_ms = ev0.elapsed_time(ev1)
+        if self.err != -1:
+            raise OtbxError(4, f"{PROJECT_ERRORS[self.err & 0xff]} at output "
+                               f"row {self.err >> 8}")
+        return [(out, nulls)]
+
+    def explain(self):
+        if self.project_ms is None:
+            return None
+        return {"project": self.project_ms}
 
 
 class GpuHashAgg(CustomScanState):

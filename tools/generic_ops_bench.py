@@ -20,6 +20,11 @@ distinct from the fused query pipelines.
                                    otbx_scan_count and to a plain-torch
                                    composition of the same quals (writes
                                    profiles/filter_ops.txt, or PATH)
+  generic_ops_bench.py --project [--out PATH]
+                                   otbx_project at 600 M rows next to a
+                                   plain-torch composition of the same
+                                   expressions (writes
+                                   profiles/project_ops.txt, or PATH)
 """
 import ctypes as C
 import os
@@ -668,8 +673,149 @@ def bench_filter(out_path):
         f.write("\n".join(lines) + "\n")
 
 
+class _ProjectCall:
+    """otbx_project with everything preallocated; expr as GpuProject takes
+    it. bytes_per_row is per OUTPUT row."""
+
+    def __init__(self, expr, sel=None, out_dtype=None):
+        self.expr, self.sel = expr, sel
+        self.n = len(sel) if sel is not None else expr.n_src
+        self.n_src = expr.n_src
+        dt = out_dtype or ex._EX_OUT_DTYPE[expr.vtype]
+        self.out = torch.empty(self.n, dtype=dt, device="cuda")
+        self.nulls = torch.empty(self.n, dtype=torch.uint8, device="cuda") \
+            if expr.nullable else None
+        self.err = torch.zeros(1, dtype=torch.int64, device="cuda")
+        self.dev = expr.to_dev()
+        self.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        seen = {}
+        for ins in expr.program():
+            if ins[0] == "col":
+                for x in ins[1:]:
+                    if x is not None:
+                        seen[x.data_ptr()] = x.element_size()
+        self.bytes_per_row = sum(seen.values()) + self.out.element_size() + \
+            (1 if self.nulls is not None else 0) + (8 if sel is not None else 0)
+
+    def __call__(self):
+        call("otbx_project", C.byref(self.dev),
+             C.c_void_p(self.sel.data_ptr()) if self.sel is not None else None,
+             C.c_int64(self.n), C.c_int64(self.n_src),
+             C.c_int32(ex._SORT_TYPE[self.out.dtype]),
+             C.c_void_p(self.out.data_ptr()),
+             C.c_void_p(self.nulls.data_ptr()) if self.nulls is not None
+             else None, C.c_void_p(self.err.data_ptr()), self.stream)
+
+
+def bench_project(out_path):
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    say("# tools/generic_ops_bench.py --project — best / worst of 5 wall time "
+        "after torch.cuda.synchronize(), columns staged, output, mask and "
+        "error slot preallocated")
+    say("# algorithmic B per output row = referenced columns and masks, each "
+        "once + output width [+ 1 output mask] [+ 8 selection entry]")
+    g = torch.Generator(device="cuda").manual_seed(17)
+    n = 600_000_000
+    price = torch.rand(n, dtype=torch.float64, device="cuda", generator=g) * 1e5
+    disc = torch.randint(0, 11, (n,), device="cuda", generator=g) \
+        .to(torch.float64) / 100
+    tax = torch.randint(0, 9, (n,), device="cuda", generator=g) \
+        .to(torch.float64) / 100
+    pnull = (torch.rand(n, device="cuda", generator=g) < 0.05).to(torch.uint8)
+    flag = torch.randint(0, 25, (n,), dtype=torch.uint8, device="cuda",
+                         generator=g)
+    date = torch.randint(0, 2500, (n,), dtype=torch.int32, device="cuda",
+                         generator=g)
+    torch.cuda.empty_cache()
+    col = ex.col
+
+    def report(tag, what, pc, torch_fn):
+        """torch_fn returns (values, mask-or-None)"""
+        pb, pw = _best_of_5(pc)
+        assert int(pc.err.item()) == -1, f"case ({tag}) raised"
+        rows, bpr = pc.n, pc.bytes_per_row
+        tbs = rows * bpr / pb / 1e12
+        say(f"({tag}) rows={rows:_} {what}: otbx_project best {pb*1e3:8.3f} ms"
+            f"  worst {pw*1e3:8.3f} ms (spread {(pw-pb)/pb*100:.1f} %)  "
+            f"{bpr} B/row algorithmic = {rows*bpr/1e9:.2f} GB  {tbs:5.2f} TB/s"
+            f" = {tbs*1e12/COPY_CEILING*100:4.1f} % of the 6.29 TB/s copy "
+            "ceiling")
+        tb, tw = _best_of_5(torch_fn)
+        ref, refmask = torch_fn()
+        same = bool(torch.equal(ref, pc.out)) and \
+            (refmask is None or bool(torch.equal(refmask, pc.nulls)))
+        say(f"    plain torch on the same columns: best {tb*1e3:8.3f} ms  "
+            f"worst {tw*1e3:8.3f} ms; torch / otbx_project time ratio: "
+            f"{tb/pb:.2f}; same result (bit for bit): {same}")
+        assert same, f"case ({tag}): torch and otbx_project disagree"
+        del ref, refmask
+        torch.cuda.empty_cache()
+        return pb
+
+    # (a) the Q1 charge expression, no masks
+    q1 = "price * (1 - disc) * (1 + tax)"
+    pc = _ProjectCall(col(price) * (1 - col(disc)) * (1 + col(tax)))
+    report("a", q1, pc, lambda: (price * (1 - disc) * (1 + tax), None))
+    del pc
+    torch.cuda.empty_cache()
+
+    # (b) the same with a 5 % null mask on price
+    def torch_b():
+        v = price * (1 - disc) * (1 + tax)
+        return v.masked_fill_(pnull != 0, 0.0), pnull.clone()
+
+    pc = _ProjectCall(col(price, pnull) * (1 - col(disc)) * (1 + col(tax)))
+    report("b", q1 + ", 5 % NULL price", pc, torch_b)
+    del pc
+    torch.cuda.empty_cache()
+
+    # (c) a CASE
+    pc = _ProjectCall(ex.case(col(flag).eq(3), col(price) * (1 - col(disc)),
+                              0.0))
+    report("c", "CASE WHEN flag = 3 THEN price * (1 - disc) ELSE 0 END", pc,
+           lambda: (torch.where(flag == 3, price * (1 - disc), 0.0), None))
+    del pc
+    torch.cuda.empty_cache()
+
+    # (d) case (a) through a selection from otbx_filter_sel
+    for c in (24, 2449):
+        fc = _FilterCall([[ex.qual_term(date, "<=", c)]])
+        fc()
+        sel = fc.sel[:fc.count()].clone()
+        del fc
+        torch.cuda.empty_cache()
+        pc = _ProjectCall(col(price) * (1 - col(disc)) * (1 + col(tax)),
+                          sel=sel)
+        report("d", f"{q1} through the selection date <= {c} "
+               f"({len(sel)/n*100:.2f} % of {n:_} rows)", pc,
+               lambda: (price[sel] * (1 - disc[sel]) * (1 + tax[sel]), None))
+        del pc, sel
+        torch.cuda.empty_cache()
+
+    # (e) integer division on the i32 column to an I32 output
+    pc = _ProjectCall(col(date) / 365, out_dtype=torch.int32)
+    report("e", "date / 365 (i32 column, I32 output)", pc,
+           lambda: (torch.div(date, 365, rounding_mode="trunc"), None))
+    del pc
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
     ex.init_device(0)
+    if "--project" in sys.argv:
+        repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        out_path = os.path.join(repo, "profiles", "project_ops.txt")
+        if "--out" in sys.argv:
+            out_path = sys.argv[sys.argv.index("--out") + 1]
+        bench_project(out_path)
+        sys.exit(0)
     if "--filter" in sys.argv:
         repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         out_path = os.path.join(repo, "profiles", "filter_ops.txt")
