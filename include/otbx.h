@@ -150,6 +150,31 @@ otbx_status otbx_stream_sync(void *stream);
 
 /* ---- staged columnar tables (device pointers; SoA — DESIGN.md §2) ---- */
 
+/* Layout of one packed Q1 code word (otbx_lineitem_dev.q1code; DESIGN.md
+ * §7b). Five bit fields, lowest first — date_off, gid, qty, disc, tax — each
+ * `*_bits` wide starting at bit `*_off`; a width of 0 means the column holds
+ * one value and the field reads as 0.
+ *   l_shipdate  = date_base + date_off field
+ *   group slot  = gid field: ('A'→0, 'N'→1, other→2) * 2 + ('F'→0, other→1)
+ *   l_quantity  = dict[code]                      as an f64 BIT PATTERN
+ *   l_discount  = dict[OTBX_Q1_DICT_MAX + code]
+ *   l_tax       = dict[2 * OTBX_Q1_DICT_MAX + code]
+ * Each dictionary is sorted by unsigned bit pattern, so codes are
+ * deterministic; +0.0 and -0.0 are two entries and NaN payloads survive.
+ * sizeof == 72. */
+#define OTBX_Q1_DICT_MAX 256
+typedef struct {
+    int32_t date_base;             /* minimum of l_shipdate */
+    int32_t date_off, date_bits;
+    int32_t gid_off, gid_bits;     /* gid_bits is always 3 */
+    int32_t qty_off, qty_bits;
+    int32_t disc_off, disc_bits;
+    int32_t tax_off, tax_bits;
+    int32_t nqty, ndisc, ntax;     /* dictionary sizes, 1..OTBX_Q1_DICT_MAX */
+    int32_t gid_present;           /* bit g set: some row has group slot g */
+    uint64_t *dict;                /* device, uint64[3 * OTBX_Q1_DICT_MAX] */
+} otbx_q1code_desc;
+
 typedef struct {
     int64_t n;
     int64_t *l_orderkey;      /* may be NULL if not staged (Q1 needs none) */
@@ -170,6 +195,14 @@ typedef struct {
     int32_t *l_orderkey32;
     int32_t *l_partkey32;     /* same compact-key cache for l_partkey
                                * (halves the Q9 filter's key stream) */
+    /* optional packed Q1 code column (otbx_build_q1codes, built once at
+     * staging): one 32-bit word per row holding the shipdate offset, the Q1
+     * group slot and dictionary codes of l_quantity / l_discount / l_tax,
+     * laid out as q1desc says. Q1 then streams this word plus
+     * l_extendedprice, 12 B/row instead of 38. NULL = Q1 reads the raw
+     * columns. q1desc is meaningful only while q1code is non-NULL. */
+    uint32_t *q1code;
+    otbx_q1code_desc q1desc;
 } otbx_lineitem_dev;
 
 typedef struct {
@@ -208,6 +241,35 @@ typedef struct {
 otbx_status otbx_build_key32(const int64_t *src_dev, int64_t n,
                              int32_t *dst32_dev, int32_t *ok_host,
                              void *stream);
+/* Plan the packed Q1 code word. Pure host code (no HIP call). Inputs: the
+ * three dictionary sizes and date_span = max(l_shipdate) - min(l_shipdate).
+ * A field's width is ceil(log2(size)) (size 1 → 0 bits), the date field has
+ * as many bits as date_span, gid always 3. *fits_host = 1 and the offsets /
+ * widths / sizes of *desc are filled (date_base, gid_present and dict are
+ * left alone) when every size is in 1..OTBX_Q1_DICT_MAX, date_span < 2^32
+ * and the widths sum to at most 32; otherwise *fits_host = 0 and *desc is
+ * untouched.
+ * OTBX_ERR_INVALID only for NULL pointers. */
+otbx_status otbx_q1code_plan(int32_t nqty, int32_t ndisc, int32_t ntax,
+                             uint64_t date_span, otbx_q1code_desc *desc,
+                             int32_t *fits_host);
+/* Build the packed Q1 code column of a staged lineitem table. Collects the
+ * distinct bit patterns of l_quantity / l_discount / l_tax and the shipdate
+ * range on the device, plans the word with otbx_q1code_plan, writes the
+ * sorted dictionaries to dict_dev (uint64[3 * OTBX_Q1_DICT_MAX]) and one
+ * word per row to codes_dev (uint32[t->n]); the encode pass decodes every
+ * word it wrote and compares it bit-for-bit with the source row.
+ * *ok_host = 1 and *desc_host filled (dict = dict_dev) on success; the
+ * caller then sets t->q1code / t->q1desc. *ok_host = 0 (caller leaves
+ * q1code NULL, Q1 keeps reading the raw columns) when the data does not
+ * fit: more than OTBX_Q1_DICT_MAX distinct patterns in a column, a column
+ * holding the all-ones pattern (the set's empty marker), widths above 32
+ * bits, a failed round trip, t->n == 0 or any Q1 column not staged.
+ * Synchronous (staging-time only), like otbx_build_key32. */
+otbx_status otbx_build_q1codes(const otbx_lineitem_dev *t,
+                               uint32_t *codes_dev, uint64_t *dict_dev,
+                               otbx_q1code_desc *desc_host, int32_t *ok_host,
+                               void *stream);
 /* build the q9rec cache from the staged columns (32 B/row into recs_dev) */
 otbx_status otbx_build_q9recs(const otbx_lineitem_dev *l, void *recs_dev,
                               void *stream);
@@ -243,8 +305,12 @@ otbx_status otbx_q1_partial(const otbx_lineitem_dev *t, int32_t cutoff_day,
                             double *sums_dev, int64_t *counts_dev,
                             void *stream, float *kernel_ms);
 /* A/B harness entry: variant 0 = 2 rows/lane, 1 = 4 rows/lane,
- * 2 = 4 rows/lane + non-temporal loads. otbx_q1_partial dispatches the
- * measured-best variant. */
+ * 2 = 4 rows/lane + non-temporal loads (all three read the raw columns,
+ * 38 B/row); 3 = the packed code column + l_extendedprice, 12 B/row, 4
+ * rows/lane; 4 = as 3 with 8 rows/lane; 5 = as 3, accumulating only the
+ * group slots in q1desc.gid_present. Variants 3 to 5 need t->q1code and
+ * return OTBX_ERR_INVALID without launching anything when it is NULL.
+ * otbx_q1_partial dispatches variant 5 when t->q1code is set, else 2. */
 otbx_status otbx_q1_partial_variant(const otbx_lineitem_dev *t,
                                     int32_t cutoff_day, double *sums_dev,
                                     int64_t *counts_dev, void *stream,

@@ -25,6 +25,25 @@ class OtbxError(RuntimeError):
         super().__init__(f"otbx error {status} ({_STATUS.get(status, '?')}) {what}")
 
 
+Q1_DICT_MAX = 256   # OTBX_Q1_DICT_MAX
+
+
+class Q1CodeDesc(C.Structure):
+    """otbx_q1code_desc (include/otbx.h): layout of the packed Q1 code word,
+    72 bytes."""
+    _fields_ = [
+        ("date_base", C.c_int32),
+        ("date_off", C.c_int32), ("date_bits", C.c_int32),
+        ("gid_off", C.c_int32), ("gid_bits", C.c_int32),
+        ("qty_off", C.c_int32), ("qty_bits", C.c_int32),
+        ("disc_off", C.c_int32), ("disc_bits", C.c_int32),
+        ("tax_off", C.c_int32), ("tax_bits", C.c_int32),
+        ("nqty", C.c_int32), ("ndisc", C.c_int32), ("ntax", C.c_int32),
+        ("gid_present", C.c_int32),
+        ("dict", C.c_void_p),
+    ]
+
+
 class LineitemDev(C.Structure):
     _fields_ = [
         ("n", C.c_int64),
@@ -37,6 +56,8 @@ class LineitemDev(C.Structure):
         ("q9rec", C.c_void_p),
         ("l_orderkey32", C.c_void_p),
         ("l_partkey32", C.c_void_p),
+        ("q1code", C.c_void_p),
+        ("q1desc", Q1CodeDesc),
     ]
 
 
@@ -150,6 +171,9 @@ def lib():
         _lib.otbx_sort_workspace_bytes.argtypes = [i64, C.c_int32, i64, szp]
         _lib.otbx_window_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_filter_workspace_bytes.argtypes = [i64, szp]
+        _lib.otbx_q1code_plan.argtypes = [
+            C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
+            C.POINTER(Q1CodeDesc), C.POINTER(C.c_int32)]
     return _lib
 
 
@@ -169,6 +193,7 @@ EXPORTED_SYMBOLS = [
     "otbx_gen_lineitem_dev", "otbx_gen_orders_dev", "otbx_gen_customer_dev",
     "otbx_gen_part_dev", "otbx_q9_workspace_bytes", "otbx_q9_partial",
     "otbx_stage_pages", "otbx_build_q9recs", "otbx_build_key32",
+    "otbx_build_q1codes", "otbx_q1code_plan",
     "otbx_scan_count", "otbx_q1_partial", "otbx_q1_partial_variant",
     "otbx_q3_workspace_bytes", "otbx_q3_partial", "otbx_filter_customer",
     "otbx_topk_by_revenue",

@@ -17,8 +17,8 @@ import math
 import torch
 
 from ._lib import (CustomerDev, ExprDev, KeysetDev, LineitemDev, OrdersDev,
-                   OtbxError, PartDev, QualDev, SortSpecDev, WindowOutDev,
-                   call, check, lib)
+                   OtbxError, PartDev, Q1_DICT_MAX, Q1CodeDesc, QualDev,
+                   SortSpecDev, WindowOutDev, call, check, lib)
 
 Q1_SLOT_ORDER = [(b"A", b"F"), (b"A", b"O"), (b"N", b"F"),
                  (b"N", b"O"), (b"R", b"F"), (b"R", b"O")]
@@ -109,7 +109,10 @@ class GpuLineitem:
         """Staging-time derived layouts (built once, outside any timed
         region, like the zone-map metadata): the int32 compact-key cache
         (otbx.h l_orderkey32) and, when partkey is staged, the Q9
-        probe-side AoS record cache (otbx.h q9rec)."""
+        probe-side AoS record cache (otbx.h q9rec); and, whenever the Q1
+        columns are staged and their value domains fit, the packed Q1 code
+        column (otbx.h q1code) that Q1 streams instead of the raw columns."""
+        self._stage_q1codes()
         if self.t.get("l_orderkey") is not None:
             self._okey32 = _build_key32(self.t["l_orderkey"])
             if self._okey32 is not None:
@@ -128,10 +131,35 @@ class GpuLineitem:
         call("otbx_build_q9recs", C.byref(self.cstruct),
              C.c_void_p(self._q9rec.data_ptr()), _stream())
 
+    Q1_COLS = ("l_quantity", "l_extendedprice", "l_discount", "l_tax",
+               "l_returnflag", "l_linestatus", "l_shipdate")
+
+    def _stage_q1codes(self):
+        """Build the packed Q1 code column (otbx_build_q1codes). The struct
+        fields are set only when the build reports success; otherwise
+        q1code stays NULL and otbx_q1_partial reads the raw columns."""
+        self._q1code = self._q1dict = None
+        if self.n == 0 or any(self.t.get(c) is None for c in self.Q1_COLS):
+            return
+        codes = torch.empty(self.n, dtype=torch.int32, device="cuda")
+        qdict = torch.empty(3 * Q1_DICT_MAX, dtype=torch.int64, device="cuda")
+        desc = Q1CodeDesc()
+        ok = C.c_int32(0)
+        call("otbx_build_q1codes", C.byref(self.cstruct),
+             C.c_void_p(codes.data_ptr()), C.c_void_p(qdict.data_ptr()),
+             C.byref(desc), C.byref(ok), _stream())
+        if not ok.value:
+            return
+        self._q1code, self._q1dict = codes, qdict   # keep the tensors alive
+        self.cstruct.q1desc = desc
+        self.cstruct.q1code = C.c_void_p(codes.data_ptr())
+
     def bytes_staged(self):
-        extra = self._q9rec.numel() if getattr(self, "_q9rec", None) is not None else 0
-        return extra + sum(v.numel() * v.element_size()
-                           for v in self.t.values() if v is not None)
+        """HBM held by the table: the columns plus every derived cache."""
+        caches = [getattr(self, a, None) for a in
+                  ("_q9rec", "_okey32", "_pkey32", "_q1code", "_q1dict")]
+        return sum(v.numel() * v.element_size()
+                   for v in list(self.t.values()) + caches if v is not None)
 
 
 class GpuOrders:

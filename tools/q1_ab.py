@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Within-probe interleaved A/B of the Q1 kernel variants (guide §5.4 rule 24):
 N rounds × variants interleaved in one process; reports median/min ms and
-checks result parity across variants. Run on the GPU box."""
+checks result parity across variants. Variants 0-2 read the raw columns
+(38 B/row), 3 to 5 the staged code column + l_extendedprice (12 B/row); the
+bandwidth printed is each variant's own physical bytes over its time.
+
+usage: q1_ab.py [SF [ROUNDS [VARIANT ...]]]   (default 100, 8, all six)"""
 import ctypes as C
 import statistics
 import sys
@@ -16,7 +20,7 @@ from opentenbase_amd._lib import call  # noqa: E402
 def main():
     sf = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-    variants = [0, 1, 2]
+    variants = [int(v) for v in sys.argv[3:]] or [0, 1, 2, 3, 4, 5]
     ex.init_device(0)
     li = ex.GpuLineitem.generate(sf * 6_000_000, with_orderkey=False)
     torch.cuda.synchronize()
@@ -32,7 +36,7 @@ def main():
         return ms.value, sums.cpu().numpy().copy(), counts.cpu().numpy().copy()
 
     # warmup + parity reference
-    ref = run(0)
+    ref = run(variants[0])
     for v in variants[1:]:
         _, s, c = run(v)
         assert (c == ref[2]).all(), f"variant {v} count mismatch"
@@ -44,8 +48,8 @@ def main():
     for r in range(rounds):
         for v in variants:
             times[v].append(run(v)[0])
-    bytes_ = li.n * 38
     for v in variants:
+        bytes_ = li.n * (38 if v < 3 else 12)
         med = statistics.median(times[v])
         mn = min(times[v])
         print(f"variant {v}: median {med:.3f} ms  min {mn:.3f} ms  "
