@@ -324,7 +324,21 @@ otbx_status otbx_q1_partial_variant(const otbx_lineitem_dev *t,
  * Outputs (device, caller-allocated):
  *   groups_dev:  capacity cap_groups entries of otbx_q3_group
  *   ngroups_dev: int64[1] — compacted group count
- * ws_dev: workspace (hash tables), size from otbx_q3_workspace_bytes. */
+ * ws_dev: workspace (hash tables), size from otbx_q3_workspace_bytes.
+ *
+ * Input domain. Every int32 date and priority is an ordinary value: day 0,
+ * negative days and any o_shippriority, INT32_MIN and -1 included. Prices
+ * and discounts are any finite doubles; a group exists as soon as one
+ * lineitem matched, whatever its revenue sums to (zero and negative sums
+ * included). Keys (c_custkey, o_custkey, o_orderkey, l_orderkey, the
+ * cust_keys_dev entries) are any int64 EXCEPT INT64_MIN, the one reserved
+ * key: the hash-path tables keep it as their empty marker, so a build row
+ * carrying it is not inserted and a probe row carrying it matches nothing.
+ * Key 0 and negative keys are ordinary keys (a column holding a negative
+ * key takes the hash path: the key-range kernels compare unsigned).
+ * c_custkey may repeat (the customer side is a key SET); o_orderkey must be
+ * unique. okey_min/okey_max, when has_minmax is set, must be the exact
+ * signed bounds of o_orderkey. */
 typedef struct {
     int64_t l_orderkey;
     double revenue;
@@ -352,7 +366,11 @@ otbx_status otbx_q3_partial(const otbx_customer_dev *c,
  * LIMIT k pre-selection; the final k-way ordering happens host-side on the
  * ≤ cap_cand candidates). hist_dev: uint32[16384] workspace (zeroed by the
  * call). ncand_dev ≥ k unless n < k; candidates are all groups with revenue
- * ≥ the selection threshold (a bit-pattern bin boundary). */
+ * ≥ the selection threshold (a bin boundary of the order-preserving bit
+ * normalisation, so any finite revenue ranks correctly: negative, zero and
+ * -0.0 == +0.0 included). *ncand_dev receives the TRUE candidate count even
+ * when it exceeds cap_cand; at most cap_cand entries of cand_dev are
+ * written, and the caller retries with a larger buffer. */
 otbx_status otbx_topk_by_revenue(const otbx_q3_group *groups_dev, int64_t n,
                                  int64_t k, otbx_q3_group *cand_dev,
                                  int64_t cap_cand, int64_t *ncand_dev,
@@ -369,7 +387,20 @@ otbx_status otbx_filter_customer(const otbx_customer_dev *c, uint8_t segment,
  * key. Dense outputs over the 7 order years (0 = 1992):
  *   sums_dev: double[7] revenue, counts_dev: int64[7]; both zeroed by the
  * call; the Coordinator merge all-gathers them like Q1's states.
- * ws: otbx_q9_workspace_bytes(nparts, norders_local, nranks). */
+ * ws: otbx_q9_workspace_bytes(nparts, norders_local, nranks).
+ *
+ * Input domain. p_partkey is a permutation of 1..p->n (any row order): the
+ * part filter is a bitmap indexed by p_partkey - 1, and l_partkey values
+ * outside [1, p->n] match nothing. o_orderkey is unique, ≥ 0, and dense
+ * enough that max - min + 1 ≤ norders * nranks; a wider range does not fit
+ * the workspace and is refused with OTBX_ERR_INVALID before any kernel
+ * runs. okey_min/okey_max, when has_minmax is set, must be exact.
+ * o_orderdate lies in [0, 2557] (the 7 calendar years of otbx_year_of_day),
+ * day 0 included; OTBX_Q9_DATE_ABSENT is the one int32 the date lookup table
+ * reserves for "no such order" (dates are stored XOR this value, so that a
+ * zeroed entry decodes to it). An empty lineitem (n == 0) may carry NULL
+ * columns. */
+#define OTBX_Q9_DATE_ABSENT ((int32_t)0x80808080u)
 otbx_status otbx_q9_workspace_bytes(int64_t nparts, int64_t norders,
                                     int64_t nlineitem, uint32_t nranks,
                                     size_t *bytes);
@@ -573,7 +604,8 @@ otbx_status otbx_agg_i64_dec(const int64_t *keys_dev,
  * Full sort of Q3 group rows by (revenue DESC, o_orderdate ASC) — the
  * tuplesort.c analog for the no-LIMIT ORDER BY case (LIMIT queries use
  * otbx_topk_by_revenue). Stable LSD radix sort; out_dev must not alias
- * groups_dev. */
+ * groups_dev. Preconditions: 0 ≤ o_orderdate < 2^16 (the date key is sorted
+ * in two 8-bit passes); revenue any non-NaN double (-0.0 ties with +0.0). */
 otbx_status otbx_order_groups_workspace_bytes(int64_t n, size_t *bytes);
 otbx_status otbx_order_groups(const otbx_q3_group *groups_dev, int64_t n,
                               otbx_q3_group *out_dev, void *ws,

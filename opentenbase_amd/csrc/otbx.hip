@@ -31,6 +31,7 @@
 #include <algorithm>   /* std::sort (Q1 code dictionaries) */
 
 #include "otbx_common.h"
+#include "otbx_sortkey.h"            /* ss_norm_f64: revenue ranking */
 #include "../../oracle/otbx_gen.h"   /* shared deterministic datagen */
 
 #define OTBX_VERSION_STR "otbx 0.1 gfx950"
@@ -1189,6 +1190,16 @@ __device__ __forceinline__ int64_t wave_append(int64_t *counter, bool pred)
                                     (unsigned long long)__popcll(mask));
     base = __shfl(base, leader, WAVE);
     return pred ? base + rank : -1;
+}
+
+/* max - min + 1 without signed overflow: key columns may span more than
+ * 2^63 (a negative key next to INT64_MAX - 1). A span that does not fit
+ * comes back as INT64_MAX, which no direct-table cap admits. */
+static int64_t key_range(int64_t mn, int64_t mx)
+{
+    if (mx < mn) return 0;
+    uint64_t span = (uint64_t)mx - (uint64_t)mn;
+    return span >= (uint64_t)INT64_MAX ? INT64_MAX : (int64_t)span + 1;
 }
 
 static inline int64_t next_pow2_host(int64_t v)
@@ -2854,7 +2865,10 @@ __global__ void k_q9_part_bitmap(const otbx_part_dev p, uint8_t typemod,
 
 /* orders date lookup: direct-addressed by (o_orderkey - mino); orderkeys are
  * dense per shard so the table is the merge of local rows (the same
- * dense-direct reasoning as Q3 — DESIGN.md §3). date ≥ 1 → 0 = absent. */
+ * dense-direct reasoning as Q3 — DESIGN.md §3). Entries hold the date
+ * XOR OTBX_Q9_DATE_ABSENT (otbx.h): the memset(0) word that no order wrote
+ * then decodes to that one reserved date value, and day 0 is an ordinary
+ * date. */
 __global__ void k_q9_odate_build(const otbx_orders_dev o, int64_t mino,
                                  int32_t *dtab)
 {
@@ -2862,11 +2876,13 @@ __global__ void k_q9_odate_build(const otbx_orders_dev o, int64_t mino,
     if (o.o_orderkey32) { /* compact-key cache: 12 -> 8 B/row stream */
         for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
              i < o.n; i += stride)
-            dtab[(int64_t)o.o_orderkey32[i] - mino] = o.o_orderdate[i];
+            dtab[(int64_t)o.o_orderkey32[i] - mino] =
+                o.o_orderdate[i] ^ OTBX_Q9_DATE_ABSENT;
     } else {
         for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
              i < o.n; i += stride)
-            dtab[o.o_orderkey[i] - mino] = o.o_orderdate[i];
+            dtab[o.o_orderkey[i] - mino] =
+                o.o_orderdate[i] ^ OTBX_Q9_DATE_ABSENT;
     }
 }
 
@@ -3122,9 +3138,9 @@ __global__ void k_q9_probe(const otbx_lineitem_dev l,
         int64_t oidx = okey - mino;
         if (oidx < 0 || oidx >= orange)
             continue;
-        int32_t date = dtab[oidx];
-        if (date == 0)
-            continue;
+        int32_t date = dtab[oidx] ^ OTBX_Q9_DATE_ABSENT;
+        if (date == OTBX_Q9_DATE_ABSENT)
+            continue; /* the memset(0) word: no such order */
         int32_t y = otbx_year_of_day(date);
         double rev = price * (1.0 - disc);
 #pragma unroll
@@ -3212,8 +3228,10 @@ otbx_status otbx_q9_partial(const otbx_part_dev *p, const otbx_orders_dev *o,
                             double *sums_dev, int64_t *counts_dev,
                             void *stream, float *kernel_ms)
 {
-    if (!p || !o || !l || !l->l_partkey || !l->l_orderkey || typemod == 0)
+    if (!p || !o || !l || typemod == 0)
         return OTBX_ERR_INVALID;
+    if (l->n > 0 && (!l->l_partkey || !l->l_orderkey))
+        return OTBX_ERR_INVALID; /* an empty table may carry no columns */
     if (l->n >= (int64_t)UINT32_MAX)
         return OTBX_ERR_INVALID;  /* u32 hit row ids; shard larger tables */
     hipStream_t s = (hipStream_t)stream;
@@ -3235,7 +3253,7 @@ otbx_status otbx_q9_partial(const otbx_part_dev *p, const otbx_orders_dev *o,
         orange = 1;
     } else if (o->has_minmax) { /* staged zone-map metadata */
         mino = o->okey_min;
-        orange = o->okey_max - o->okey_min + 1;
+        orange = key_range(o->okey_min, o->okey_max);
     } else {
         HIP_CHECK(hipMemsetAsync(d_mm, 0x7f, 8, s));
         HIP_CHECK(hipMemsetAsync(d_mm + 1, 0, 8, s));
@@ -3244,7 +3262,7 @@ otbx_status otbx_q9_partial(const otbx_part_dev *p, const otbx_orders_dev *o,
         HIP_CHECK(hipMemcpyAsync(h_mm, d_mm, 16, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         mino = h_mm[0];
-        orange = h_mm[1] - h_mm[0] + 1;
+        orange = key_range(h_mm[0], h_mm[1]);
     }
     /* Grace-style partkey slices: each pass rebuilds the bitmap for one
      * key range, re-streams l_partkey, and gathers only rows whose key
@@ -3258,6 +3276,11 @@ otbx_status otbx_q9_partial(const otbx_part_dev *p, const otbx_orders_dev *o,
     int64_t npasses = (p->n + slice - 1) / slice;
     if (npasses < 1) npasses = 1;
     size_t bm_bytes = align64_sz(8 * (size_t)((slice + 63) / 64));
+    /* a range the workspace cannot hold (sparse keys, or keys outside the
+     * documented domain that the unsigned minmax misreads) is refused here,
+     * before any kernel indexes the date table */
+    if (orange <= 0 || (uint64_t)orange > ws_bytes / 4)
+        return OTBX_ERR_INVALID;
     size_t dt_bytes = align64_sz((size_t)orange * 4);
     size_t need = bm_bytes + dt_bytes + 64 +
                   (size_t)(l->n > 0 ? l->n : 1) * 4;
@@ -3326,9 +3349,9 @@ otbx_status otbx_q9_partial(const otbx_part_dev *p, const otbx_orders_dev *o,
  * Full ordering of Q3 group rows: ORDER BY revenue DESC, o_orderdate ASC
  * (tuplesort.c analog). Stable LSD radix sort over (key u64, idx u32) pairs,
  * 8-bit digits, two stages chained by stability:
- *   stage A: date ASC  (2 passes — dates < 2^16)
- *   stage B: ~bits(revenue) ASC ≡ revenue DESC (8 passes; revenue > 0 so the
- *            raw IEEE bit pattern is order-preserving)
+ *   stage A: date ASC  (2 passes — precondition in otbx.h: 0 ≤ date < 2^16)
+ *   stage B: ~ss_norm_f64(revenue) ASC ≡ revenue DESC (8 passes; the
+ *            normalisation is order-preserving for every sign, -0 == +0)
  * Stable scatter: per-wave 8-ballot multi-split rank + per-digit wave/round
  * prefix counters in LDS — lane order preserved, so every pass is stable.
  */
@@ -3496,7 +3519,7 @@ __global__ void k_rs_key_revdesc(const otbx_q3_group *__restrict__ g,
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += stride)
-        keys[i] = ~(unsigned long long)__double_as_longlong(g[idx[i]].revenue);
+        keys[i] = ~ss_norm_f64(g[idx[i]].revenue);
 }
 
 __global__ void k_rs_iota(uint32_t *idx, int64_t n)
@@ -4297,7 +4320,22 @@ otbx_status otbx_join_i64(const int64_t *bkeys, const uint8_t *bnull, int64_t nb
 
 /* ================= TPC-H Q3 DN fragment ================= */
 
-/* keyset table (filtered customer): custkey ≥ 1 → EMPTY = 0 */
+/* The Q3 hash tables (customer keyset, orders table, group table) are
+ * cleared with memset(0) and claim slots by CAS on the key word, so one
+ * 64-bit pattern has to mean "empty". Keys are stored with the sign bit
+ * flipped (q3_kenc): the empty word 0 then stands for INT64_MIN, the one key
+ * value otbx.h reserves, and key 0 and negative keys are ordinary keys.
+ * Hashing stays on the raw key. */
+__device__ __forceinline__ unsigned long long q3_kenc(int64_t k)
+{
+    return (unsigned long long)k ^ 0x8000000000000000ull;
+}
+__device__ __forceinline__ int64_t q3_kdec(unsigned long long v)
+{
+    return (int64_t)(v ^ 0x8000000000000000ull);
+}
+
+/* keyset table (filtered customer): stored word q3_kenc(custkey), EMPTY = 0 */
 __global__ void k_keyset_build(const int64_t *__restrict__ keys, int64_t n,
                                unsigned long long *tab, int64_t cap)
 {
@@ -4305,8 +4343,8 @@ __global__ void k_keyset_build(const int64_t *__restrict__ keys, int64_t n,
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += stride) {
-        unsigned long long k = (unsigned long long)keys[i];
-        int64_t s = (int64_t)(d_hash_i64((int64_t)k) & (uint64_t)mask);
+        unsigned long long k = q3_kenc(keys[i]);
+        int64_t s = (int64_t)(d_hash_i64(keys[i]) & (uint64_t)mask);
         for (;;) {
             unsigned long long old = atomicCAS(&tab[s], 0ull, k);
             if (old == 0ull || old == k) break; /* dedupe: set semantics */
@@ -4327,8 +4365,8 @@ __global__ void k_keyset_build_filter(const int64_t *__restrict__ keys,
          i += stride) {
         if (seg[i] != want)
             continue;
-        unsigned long long k = (unsigned long long)keys[i];
-        int64_t s = (int64_t)(d_hash_i64((int64_t)k) & (uint64_t)mask);
+        unsigned long long k = q3_kenc(keys[i]);
+        int64_t s = (int64_t)(d_hash_i64(keys[i]) & (uint64_t)mask);
         for (;;) {
             unsigned long long old = atomicCAS(&tab[s], 0ull, k);
             if (old == 0ull || old == k) break;
@@ -4344,13 +4382,15 @@ __device__ __forceinline__ bool d_keyset_probe(const unsigned long long *tab,
     int64_t s = (int64_t)(d_hash_i64(key) & (uint64_t)mask);
     for (;;) {
         unsigned long long v = tab[s];
-        if (v == 0ull) return false;
-        if (v == (unsigned long long)key) return true;
+        if (v == 0ull) return false; /* empty first: a probe key that
+                                      * encodes to 0 can never hit */
+        if (v == q3_kenc(key)) return true;
         s = (s + 1) & mask;
     }
 }
 
-/* orders hash table: slot {okey (EMPTY=0), date, prio}; o_orderkey unique */
+/* orders hash table: slot {q3_kenc(okey) (EMPTY=0), date, prio};
+ * o_orderkey unique */
 struct ord_slot {
     unsigned long long okey;
     int32_t date;
@@ -4535,11 +4575,14 @@ __global__ void k_ord_insert(const otbx_orders_dev o,
     for (int64_t ci = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; ci < n;
          ci += stride) {
         int64_t i = cand[ci];
-        unsigned long long k = (unsigned long long)o.o_orderkey[i];
-        uint64_t h = d_hash_i64((int64_t)k);
+        int64_t rk = o.o_orderkey[i];
+        unsigned long long k = q3_kenc(rk);
+        uint64_t h = d_hash_i64(rk);
         if (npasses > 1 && (uint32_t)(h >> 32) % npasses != pass)
             continue;
-        d_bloom_set(bloom, bloom_words, (int64_t)k);
+        if (k == 0ull)
+            continue; /* reserved key (otbx.h): never inserted, never hit */
+        d_bloom_set(bloom, bloom_words, rk);
         int64_t s = (int64_t)(h & (uint64_t)mask);
         while (atomicCAS(&tab[s].okey, 0ull, k) != 0ull)
             s = (s + 1) & mask;      /* keys unique: claim exactly one slot */
@@ -4576,20 +4619,40 @@ __global__ void k_ord_count_pass(const otbx_orders_dev o,
  * traffic that bounds the hash path collapses to streaming. The reference
  * always hashes (nodeHash.c); on MI355X the locality is worth preserving.
  * Fallback to the bloom+hash path above when the range is too wide
- * (sparse keys). Empty marker in ptab: packed payload is
- * date | prio<<32 with date ≥ 1, so 0 = empty. */
+ * (sparse keys). The packed payload date | prio<<32 has no reserved
+ * value (day 0 with priority 0 packs to 0): presence lives in the bitmap
+ * alone. */
 #define OTBX_DIRECT_CAP_DEFAULT (1ll << 29)
 
 /* direct-table entry: revenue accumulator + packed (date|prio<<32) payload
  * INTERLEAVED so the insert's zero+payload store, the probe's payload read
  * + revenue atomicAdd, and the compaction's gather each touch ONE cache
  * line per entry instead of two (the split ptab/rtab layout cost a line
- * each). 0 payload/rev = empty under the legacy memset mode; the default
- * mode is bitmap-authoritative and never reads unset entries. */
+ * each). Every mode is bitmap-authoritative: entries at unset bits are
+ * stale and never emitted. */
 struct q3_rec {
     double rev;
     unsigned long long pl;
 };
+
+/* "Some lineitem matched" is carried by the accumulator's sign bit, not by
+ * its value: the build side stores -0.0, and every probe add is a value
+ * with its zero normalised to +0.0 (q3_pos0). Under round-to-nearest
+ * -0.0 + x is x for x != 0, -0.0 + +0.0 is +0.0, and an exact cancellation
+ * x + -x is +0.0, so the bit pattern of -0.0 survives if and only if no add
+ * happened. A group whose revenue sums to zero is therefore still a group.
+ * Costs no extra table traffic (a second "matched" bitmap would add one
+ * atomic per hit). */
+#define Q3_REV_UNMATCHED (-0.0)
+__device__ __forceinline__ double q3_pos0(double x)
+{
+    return x == 0.0 ? 0.0 : x;
+}
+__device__ __forceinline__ bool q3_matched(double rev)
+{
+    return (unsigned long long)__double_as_longlong(rev) !=
+           0x8000000000000000ull;
+}
 
 /* single-pass orders side for the common dense case: when the UNFILTERED
  * orderkey range already fits the direct table (known from a cheap minmax
@@ -4657,7 +4720,7 @@ __global__ void k_ord_filter_insert_fused(
             if (idx < 0 || idx >= range) continue;
             atomicOr(&bitmap[idx >> 6], 1ull << (idx & 63));
             q3_rec r;
-            r.rev = 0.0; /* survivor-slot zeroing (see k_ord_insert_direct) */
+            r.rev = Q3_REV_UNMATCHED; /* see k_ord_insert_direct */
             r.pl = (unsigned long long)(uint32_t)ds[j] |
                    ((unsigned long long)(uint32_t)prio[j] << 32);
             grec[idx] = r; /* one 16-B store on one line */
@@ -4681,7 +4744,7 @@ __global__ void k_ord_filter_insert_fused(
             if (idx < 0 || idx >= range) continue;
             atomicOr(&bitmap[idx >> 6], 1ull << (idx & 63));
             q3_rec r;
-            r.rev = 0.0;
+            r.rev = Q3_REV_UNMATCHED;
             r.pl = (unsigned long long)(uint32_t)o.o_orderdate[i] |
                    ((unsigned long long)(uint32_t)o.o_shippriority[i] << 32);
             grec[idx] = r;
@@ -4706,10 +4769,10 @@ __global__ void k_ord_insert_direct(const otbx_orders_dev o,
             continue; /* outside this grace pass's key sub-range */
         atomicOr(&bitmap[idx >> 6], 1ull << (idx & 63));
         q3_rec r;
-        r.rev = 0.0; /* survivor-slot zeroing: replaces the whole-range
-                      * memset (orderkeys unique -> one writer per idx;
-                      * unset-bit entries are never read: compaction is
-                      * bitmap-authoritative) */
+        r.rev = Q3_REV_UNMATCHED; /* survivor-slot reset: replaces a
+                      * whole-range memset (orderkeys unique -> one writer
+                      * per idx; unset-bit entries are never read:
+                      * compaction is bitmap-authoritative) */
         r.pl = (unsigned long long)(uint32_t)o.o_orderdate[i] |
                ((unsigned long long)(uint32_t)o.o_shippriority[i] << 32);
         grec[idx] = r;
@@ -4752,7 +4815,6 @@ __global__ void k_q3_scan_probe_agg_direct(const otbx_lineitem_dev l,
             ky[0] = ka.x; ky[1] = ka.y; ky[2] = kb.x; ky[3] = kb.y;
         }
         int32_t ds[4] = {d.x, d.y, d.z, d.w};
-        unsigned long long pl[4];
         bool m[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -4761,9 +4823,6 @@ __global__ void k_q3_scan_probe_agg_direct(const otbx_lineitem_dev l,
             int64_t bidx = pass ? idx : 0;
             unsigned long long w = bitmap[bidx >> 6];
             m[j] = pass && ((w >> (bidx & 63)) & 1ull);
-            /* payload read only where the bitmap passed (exact filter):
-             * clustered keys keep these on few lines */
-            pl[j] = m[j] ? grec[idx].pl : 0ull;
         }
         /* in-lane run combine: lineitem rows arrive clustered by orderkey
          * (~4 rows/order), so a lane's quad usually hits one or two keys —
@@ -4774,7 +4833,8 @@ __global__ void k_q3_scan_probe_agg_direct(const otbx_lineitem_dev l,
         bool run_valid = false;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            if (!m[j] || pl[j] == 0ull)
+            if (!m[j]) /* the bitmap is the presence authority: any
+                        * payload value, 0 included, is a real order */
                 continue;
             myhits++;
             int64_t i = q * 4 + j;
@@ -4783,14 +4843,14 @@ __global__ void k_q3_scan_probe_agg_direct(const otbx_lineitem_dev l,
                 run_sum += rev;
             } else {
                 if (run_valid)
-                    atomicAdd(&grec[run_key - mino].rev, run_sum);
+                    atomicAdd(&grec[run_key - mino].rev, q3_pos0(run_sum));
                 run_key = ky[j];
                 run_sum = rev;
                 run_valid = true;
             }
         }
         if (run_valid)
-            atomicAdd(&grec[run_key - mino].rev, run_sum);
+            atomicAdd(&grec[run_key - mino].rev, q3_pos0(run_sum));
     }
     /* tail rows */
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -4800,12 +4860,9 @@ __global__ void k_q3_scan_probe_agg_direct(const otbx_lineitem_dev l,
                 continue;
             if (!((bitmap[idx >> 6] >> (idx & 63)) & 1ull))
                 continue;
-            unsigned long long pv = grec[idx].pl;
-            if (pv == 0ull)
-                continue;
             myhits++;
             double rev = l.l_extendedprice[i] * (1.0 - l.l_discount[i]);
-            atomicAdd(&grec[idx].rev, rev);
+            atomicAdd(&grec[idx].rev, q3_pos0(rev));
         }
     }
     for (int off = WAVE / 2; off > 0; off >>= 1)
@@ -4842,7 +4899,8 @@ __global__ __launch_bounds__(1024) void k_q3_compact_word(
         /* drop bits past range in the last word */
         if (w0 == nwords - 1 && (range & 63))
             w &= (1ull << (range & 63)) - 1ull;
-        /* count survivors in my word (rev != 0 filters no-match builds) */
+        /* count survivors in my word (q3_matched drops build rows that no
+         * lineitem hit) */
         int64_t base_e = w0 * 64;
         int mycnt = 0;
         unsigned long long wm = w;
@@ -4850,7 +4908,7 @@ __global__ __launch_bounds__(1024) void k_q3_compact_word(
         while (wm) {
             int b = __builtin_ctzll(wm);
             wm &= wm - 1;
-            if (grec[base_e + b].rev != 0.0) {
+            if (q3_matched(grec[base_e + b].rev)) {
                 keep |= 1ull << b;
                 mycnt++;
             }
@@ -4961,9 +5019,9 @@ __global__ __launch_bounds__(1024) void k_q3_compact_tile(
             int mycnt = 0;
             /* bitmap is the presence authority (records are NOT memset
              * per step; stale entries live at unset-bit positions);
-             * rev != 0 then drops build rows with no probe match
-             * (revenue > 0 by domain: price > 0, disc < 1). The record
-             * loads only run near set bits — most quads fast-skip. */
+             * q3_matched then drops build rows with no probe match (the
+             * revenue VALUE says nothing: a group may sum to zero). The
+             * record loads only run near set bits — most quads fast-skip. */
             if (r0 + 3 < range) {
                 unsigned long long w = bitmap[r0 >> 6] >> (r0 & 63);
                 if (w & 0xfull) {
@@ -4972,7 +5030,7 @@ __global__ __launch_bounds__(1024) void k_q3_compact_tile(
                     const v2d *gr2 = (const v2d *)&grec[r0];
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
-                        m[j] = ((w >> j) & 1ull) && gr2[j].x != 0.0;
+                        m[j] = ((w >> j) & 1ull) && q3_matched(gr2[j].x);
                         mycnt += m[j];
                     }
                 }
@@ -4980,7 +5038,7 @@ __global__ __launch_bounds__(1024) void k_q3_compact_tile(
                 for (int j = 0; j < 4 && r0 + j < range; j++) {
                     int64_t i = r0 + j;
                     m[j] = ((bitmap[i >> 6] >> (i & 63)) & 1ull) &&
-                           grec[i].rev != 0.0;
+                           q3_matched(grec[i].rev);
                     mycnt += m[j];
                 }
             }
@@ -5027,12 +5085,16 @@ __global__ __launch_bounds__(1024) void k_q3_compact_tile(
 }
 
 __global__ void k_q3_compact_direct(const q3_rec *__restrict__ grec,
+                                    const unsigned long long *__restrict__ bitmap,
                                     int64_t range, int64_t mino,
                                     otbx_q3_group *out, int64_t cap_out,
                                     int64_t *ngroups)
 {
-    /* legacy (memset-dependent) block-chunk compaction over the
-     * interleaved record table: one 16-B load per entry on each pass */
+    /* legacy block-chunk compaction over the interleaved record table:
+     * one 16-B load per entry on each pass. Presence comes from the bitmap
+     * and "matched" from q3_matched, as in the other two kernels; the
+     * whole-range memset only keeps the loads at unset-bit entries
+     * defined. */
     int64_t per_block = (range + gridDim.x - 1) / gridDim.x;
     int64_t lo = blockIdx.x * per_block;
     int64_t hi = lo + per_block < range ? lo + per_block : range;
@@ -5040,7 +5102,8 @@ __global__ void k_q3_compact_direct(const q3_rec *__restrict__ grec,
     __shared__ int64_t tbase[257];
     int64_t my = 0;
     for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x)
-        my += grec[i].rev != 0.0;
+        my += ((bitmap[i >> 6] >> (i & 63)) & 1ull) &&
+              q3_matched(grec[i].rev);
     tcnt[threadIdx.x] = my;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -5057,7 +5120,7 @@ __global__ void k_q3_compact_direct(const q3_rec *__restrict__ grec,
     int64_t pos = tbase[256] + tbase[threadIdx.x];
     for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
         q3_rec r = grec[i];
-        if (r.rev != 0.0) {
+        if (((bitmap[i >> 6] >> (i & 63)) & 1ull) && q3_matched(r.rev)) {
             if (pos < cap_out) {
                 out[pos].l_orderkey = mino + i;
                 out[pos].revenue = r.rev;
@@ -5069,8 +5132,8 @@ __global__ void k_q3_compact_direct(const q3_rec *__restrict__ grec,
     }
 }
 
-/* group table for the partial agg: slot {okey (EMPTY=0 claim via CAS),
- * date, prio, revenue (f64 atomic)} */
+/* group table for the partial agg: slot {q3_kenc(okey) (EMPTY=0 claim via
+ * CAS), date, prio, revenue (f64 atomic)} */
 struct q3g_slot {
     unsigned long long okey;
     int32_t date;
@@ -5224,16 +5287,19 @@ __global__ void k_q3_probe_agg(const otbx_lineitem_dev l,
              * broadcasts from its nearest leader */
             unsigned long long v = sv[k].x;
             unsigned long long payload = sv[k].y;
+            unsigned long long ek = q3_kenc(key[k]);
             if (lead[k]) {
                 int64_t s = slot[k];
-                while (v != 0ull && v != (unsigned long long)key[k]) {
+                while (v != 0ull && v != ek) {
                     s = (s + 1) & omask;      /* rare: collision walk */
                     ulonglong2 sv2 = otab2[s];
                     v = sv2.x;
                     payload = sv2.y;
                 }
             }
-            int hitv = v == (unsigned long long)key[k];
+            /* an empty slot ends the walk and is never a hit, whatever the
+             * probe key encodes to */
+            int hitv = v != 0ull && v == ek;
             int lidx = lead[k] ? lane : -1;
             for (int st = 1; st < WAVE; st <<= 1) {
                 int u = __shfl_up(lidx, st, WAVE);
@@ -5250,15 +5316,14 @@ __global__ void k_q3_probe_agg(const otbx_lineitem_dev l,
             double rev = ep[k] * (1.0 - dc[k]);
             int64_t g = (int64_t)(d_hash_i64(key[k]) & (uint64_t)gmask);
             for (;;) {
-                unsigned long long old = atomicCAS(&gtab[g].okey, 0ull,
-                                                   (unsigned long long)key[k]);
+                unsigned long long old = atomicCAS(&gtab[g].okey, 0ull, ek);
                 if (old == 0ull) {
                     gtab[g].date = date;  /* winner writes payload; read by
                                            * the compact kernel (next launch) */
                     gtab[g].prio = prio;
                     break;
                 }
-                if (old == (unsigned long long)key[k]) break;
+                if (old == ek) break;
                 g = (g + 1) & gmask;
             }
             atomicAdd(&gtab[g].revenue, rev);
@@ -5299,7 +5364,7 @@ __global__ void k_q3_compact(const q3g_slot *gtab, int64_t gcap,
     for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
         if (gtab[i].okey != 0ull) {
             if (pos < cap_out) {
-                out[pos].l_orderkey = (int64_t)gtab[i].okey;
+                out[pos].l_orderkey = q3_kdec(gtab[i].okey);
                 out[pos].revenue = gtab[i].revenue;
                 out[pos].o_orderdate = gtab[i].date;
                 out[pos].o_shippriority = gtab[i].prio;
@@ -5643,7 +5708,7 @@ otbx_status otbx_q3_partial(const otbx_customer_dev *c, const otbx_orders_dev *o
     HIP_CHECK(hipStreamSynchronize(s));
     int64_t ncust_f = cust_keys_dev ? ncust_keys : h_cnt[0];
     cmin = h_cnt[6];
-    crange = h_cnt[7] - h_cnt[6] + 1;
+    crange = key_range(h_cnt[6], h_cnt[7]);
     bool cust_direct = ncust_f > 0 && crange > 0 && crange <= dcap_c &&
                        !force_hash;
     if (cust_direct) {
@@ -5657,7 +5722,9 @@ otbx_status otbx_q3_partial(const otbx_customer_dev *c, const otbx_orders_dev *o
             hipLaunchKernelGGL(k_cust_bitmap_filter, dim3(grid_for(c->n, 256)),
                                dim3(256), 0, s, *c, segment, cmin, cbitmap);
     } else {
-        ccap = fit_cap(ncust_f > 0 ? ncust_f : 16);
+        ccap = fit_cap(ncust_f); /* ≤ the ccap_w region: ncust_f ≤ ncust
+                                  * (an empty set used to get fit_cap(16)
+                                  * = 32 slots in a 16-slot region) */
         HIP_CHECK(hipMemsetAsync(ctab, 0, (size_t)ccap * 8, s));
         if (cust_keys_dev) {
             if (ncust_keys > 0)
@@ -5678,14 +5745,14 @@ otbx_status otbx_q3_partial(const otbx_customer_dev *c, const otbx_orders_dev *o
      * no candidate list, no separate insert, no second host sync. */
     int64_t mino_all = o->has_minmax ? o->okey_min : h_cnt[4];
     int64_t range_all =
-        o->n > 0 ? (o->has_minmax ? o->okey_max : h_cnt[5]) - mino_all + 1
+        o->n > 0 ? key_range(mino_all, o->has_minmax ? o->okey_max : h_cnt[5])
                  : 0;
     if (o->n > 0 && range_all > 0 && range_all <= dcap && !force_hash) {
         HIP_CHECK(hipMemsetAsync(dbitmap, 0,
                                  (size_t)(range_all / 64 + 8) * 8, s));
         if (q3_compact_legacy()) {
-            /* legacy compaction scans rev != 0 over the whole range, so
-             * it needs the full-range zeroing the default path skips */
+            /* legacy compaction loads every record of the range, so it
+             * keeps the full-range zeroing the default path skips */
             HIP_CHECK(hipMemsetAsync(dgrec, 0, (size_t)range_all * 16, s));
         }
         if (o->o_orderkey32 && o->o_custkey32)
@@ -5713,7 +5780,7 @@ otbx_status otbx_q3_partial(const otbx_customer_dev *c, const otbx_orders_dev *o
         if (q3_compact_legacy())
             hipLaunchKernelGGL(k_q3_compact_direct,
                                dim3(grid_for(range_all, 256)), dim3(256), 0,
-                               s, dgrec, range_all, mino_all,
+                               s, dgrec, dbitmap, range_all, mino_all,
                                groups_dev, cap_groups, ngroups_dev);
         else if (q3_compact_tile_sel())
             hipLaunchKernelGGL(k_q3_compact_tile, dim3(2048), dim3(1024), 0,
@@ -5741,7 +5808,7 @@ otbx_status otbx_q3_partial(const otbx_customer_dev *c, const otbx_orders_dev *o
     {
     int64_t nof = h_cnt[1];
     int64_t mino = h_cnt[4], maxo = h_cnt[5];
-    int64_t range = maxo - mino + 1;
+    int64_t range = key_range(mino, maxo);
     /* grace-style multi-pass (SURVEY §8f.4 analog): when the build side's
      * key range exceeds the direct tables' capacity, split it into ≤64
      * sub-ranges and run the direct pipeline once per sub-range — bounded
@@ -5749,7 +5816,7 @@ otbx_status otbx_q3_partial(const otbx_customer_dev *c, const otbx_orders_dev *o
      * batch spill tradeoff, nodeHash.c:1086). */
     int64_t npasses = 1;
     if (nof > 0 && range > dcap) {
-        npasses = (range + dcap - 1) / dcap;
+        npasses = range / dcap + (range % dcap != 0);
         if (npasses > 64) npasses = 1; /* too sparse: hash path */
     }
     bool use_direct = nof > 0 && range > 0 &&
@@ -5793,8 +5860,8 @@ otbx_status otbx_q3_partial(const otbx_customer_dev *c, const otbx_orders_dev *o
             if (q3_compact_legacy())
                 hipLaunchKernelGGL(k_q3_compact_direct,
                                    dim3(grid_for(prange, 256)), dim3(256), 0,
-                                   s, dgrec, prange, pmin, groups_dev,
-                                   cap_groups, ngroups_dev);
+                                   s, dgrec, dbitmap, prange, pmin,
+                                   groups_dev, cap_groups, ngroups_dev);
             else if (q3_compact_tile_sel())
                 hipLaunchKernelGGL(k_q3_compact_tile, dim3(2048), dim3(1024),
                                    0, s, dgrec, dbitmap, prange, pmin,
@@ -5879,14 +5946,14 @@ emit:
 }
 
 /* ---- top-k by revenue: bit-pattern histogram selection ----
- * For revenue ≥ 0, the raw IEEE-754 bit pattern is order-preserving, so the
- * top 14 bits (sign+exp+mantissa head) give 16384 monotonic bins; select the
- * threshold bin from the suffix sum, collect candidates ≥ threshold. */
+ * ss_norm_f64 (otbx_sortkey.h) maps a double to bits that compare as the
+ * doubles do, negative revenue and -0.0 included, so its top 14 bits
+ * (sign+exp+mantissa head) give 16384 monotonic bins; select the threshold
+ * bin from the suffix sum, collect candidates ≥ threshold. */
 
 __device__ __forceinline__ uint32_t rev_bin(double r)
 {
-    unsigned long long b = __double_as_longlong(r);
-    return (uint32_t)(b >> 50); /* positive doubles: monotonic */
+    return (uint32_t)(ss_norm_f64(r) >> 50);
 }
 
 __global__ void k_topk_hist(const otbx_q3_group *__restrict__ g, int64_t n,

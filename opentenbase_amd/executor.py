@@ -42,15 +42,46 @@ def device_synchronize():
 
 # ---------------- staged tables (device-resident column cache) -------------
 
-def _build_key32(src_tensor):
+def _build_key32(src_tensor, src_ptr=None):
     """Staging-time compact-key cache (otbx.h otbx_build_key32): int32 copy
     of an i64 key column, or None if any key falls outside [0, 2^31)."""
     n = src_tensor.numel()
-    dst = torch.empty(n, dtype=torch.int32, device="cuda")
+    dst = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
     ok = C.c_int32(0)
-    call("otbx_build_key32", C.c_void_p(src_tensor.data_ptr()), C.c_int64(n),
+    call("otbx_build_key32",
+         C.c_void_p(src_ptr or src_tensor.data_ptr()), C.c_int64(n),
          C.c_void_p(dst.data_ptr()), C.byref(ok), _stream())
     return dst if ok.value else None
+
+
+class _Col:
+    """Device column of n rows: .t is the n-row tensor, .ptr its address.
+    An empty table still gets a one-element allocation behind it, because
+    the C-ABI reads a NULL column pointer as "not staged" (and torch gives
+    an empty tensor a NULL data_ptr)."""
+
+    def __init__(self, n, dtype, device="cuda"):
+        self.base = torch.empty(max(n, 1), dtype=dtype, device=device)
+        self.t = self.base[:n]
+        self.ptr = self.base.data_ptr()
+
+
+def _h2d_cols(t, cols):
+    """Copy host columns (dict of numpy arrays keyed like t.t) into the
+    staged table's device columns: the otbx_stage_table flow of
+    GpuLineitem.from_host. An absent device column (None) is skipped."""
+    import numpy as np
+    for name, dst in t.t.items():
+        if dst is None:
+            continue
+        src = np.ascontiguousarray(
+            cols[name], dtype=torch.empty(0, dtype=dst.dtype).numpy().dtype)
+        assert len(src) == t.n, (name, len(src), t.n)
+        if src.nbytes:
+            call("otbx_memcpy_h2d", C.c_void_p(dst.data_ptr()),
+                 src.ctypes.data_as(C.c_void_p), C.c_size_t(src.nbytes),
+                 _stream())
+    call("otbx_stream_sync", _stream())  # host buffers may be freed
 
 
 class GpuLineitem:
@@ -64,13 +95,15 @@ class GpuLineitem:
                  device="cuda"):
         self.n = n
         self.t = {}
+        self._cols = {}
         for name, dt in self.COLS:
             if (name == "l_orderkey" and not with_orderkey) or                (name == "l_partkey" and not with_partkey):
                 self.t[name] = None
                 continue
-            self.t[name] = torch.empty(n, dtype=dt, device=device)
+            self._cols[name] = _Col(n, dt, device)
+            self.t[name] = self._cols[name].t
         self.cstruct = LineitemDev(
-            n=n, **{k: C.c_void_p(0 if v is None else v.data_ptr())
+            n=n, **{k: C.c_void_p(0 if v is None else self._cols[k].ptr)
                     for k, v in self.t.items()})
 
     @classmethod
@@ -90,18 +123,9 @@ class GpuLineitem:
         arrays (the provider's heap→SoA staging output) → device column
         cache via otbx_memcpy_h2d. cols: dict of numpy arrays keyed like
         COLS. Returns the staged table; PCIe-inclusive, one-time."""
-        import numpy as np
         n = len(cols["l_shipdate"])
         t = cls(n, with_orderkey=with_orderkey, with_partkey=with_partkey)
-        for name, dt in cls.COLS:
-            if t.t[name] is None:
-                continue
-            src = np.ascontiguousarray(cols[name])
-            assert src.nbytes == t.t[name].numel() * t.t[name].element_size()
-            call("otbx_memcpy_h2d", C.c_void_p(t.t[name].data_ptr()),
-                 src.ctypes.data_as(C.c_void_p), C.c_size_t(src.nbytes),
-                 _stream())
-        call("otbx_stream_sync", _stream())  # host buffers may be freed
+        _h2d_cols(t, cols)
         t._stage_caches()
         return t
 
@@ -114,18 +138,20 @@ class GpuLineitem:
         column (otbx.h q1code) that Q1 streams instead of the raw columns."""
         self._stage_q1codes()
         if self.t.get("l_orderkey") is not None:
-            self._okey32 = _build_key32(self.t["l_orderkey"])
+            self._okey32 = _build_key32(self.t["l_orderkey"],
+                                        self._cols["l_orderkey"].ptr)
             if self._okey32 is not None:
                 self.cstruct.l_orderkey32 = C.c_void_p(
                     self._okey32.data_ptr())
         if self.t.get("l_partkey") is not None:
-            self._pkey32 = _build_key32(self.t["l_partkey"])
+            self._pkey32 = _build_key32(self.t["l_partkey"],
+                                        self._cols["l_partkey"].ptr)
             if self._pkey32 is not None:
                 self.cstruct.l_partkey32 = C.c_void_p(
                     self._pkey32.data_ptr())
         if self.t.get("l_partkey") is None or self.t.get("l_orderkey") is None:
             return
-        self._q9rec = torch.empty(self.n * 32, dtype=torch.uint8,
+        self._q9rec = torch.empty(max(self.n, 1) * 32, dtype=torch.uint8,
                                   device="cuda")
         self.cstruct.q9rec = C.c_void_p(self._q9rec.data_ptr())
         call("otbx_build_q9recs", C.byref(self.cstruct),
@@ -165,14 +191,15 @@ class GpuLineitem:
 class GpuOrders:
     def __init__(self, n, device="cuda"):
         self.n = n
-        self.t = {
-            "o_orderkey": torch.empty(n, dtype=torch.int64, device=device),
-            "o_custkey": torch.empty(n, dtype=torch.int64, device=device),
-            "o_orderdate": torch.empty(n, dtype=torch.int32, device=device),
-            "o_shippriority": torch.empty(n, dtype=torch.int32, device=device),
+        self._cols = {
+            "o_orderkey": _Col(n, torch.int64, device),
+            "o_custkey": _Col(n, torch.int64, device),
+            "o_orderdate": _Col(n, torch.int32, device),
+            "o_shippriority": _Col(n, torch.int32, device),
         }
+        self.t = {k: c.t for k, c in self._cols.items()}
         self.cstruct = OrdersDev(
-            n=n, **{k: C.c_void_p(v.data_ptr()) for k, v in self.t.items()})
+            n=n, **{k: C.c_void_p(c.ptr) for k, c in self._cols.items()})
 
     @classmethod
     def generate(cls, n_global, ncust_global, rank=0, nranks=1,
@@ -184,9 +211,30 @@ class GpuOrders:
         t._stage_key32()
         return t
 
+    @classmethod
+    def from_host(cls, cols, minmax=True):
+        """Stage an orders table from host columns (dict of numpy arrays:
+        o_orderkey, o_custkey, o_orderdate, o_shippriority), as
+        GpuLineitem.from_host does. minmax=True fills the zone-map metadata
+        (okey_min/okey_max/has_minmax) from the host column, the way a
+        provider computes it while walking pages; minmax=False leaves
+        has_minmax = 0, so the fragments run their own minmax kernel."""
+        import numpy as np
+        t = cls(len(cols["o_orderkey"]))
+        _h2d_cols(t, cols)
+        if minmax and t.n > 0:
+            ok = np.asarray(cols["o_orderkey"], dtype=np.int64)
+            t.cstruct.okey_min = int(ok.min())
+            t.cstruct.okey_max = int(ok.max())
+            t.cstruct.has_minmax = 1
+        t._stage_key32()
+        return t
+
     def _stage_key32(self):
-        self._okey32 = _build_key32(self.t["o_orderkey"])
-        self._ckey32 = _build_key32(self.t["o_custkey"])
+        self._okey32 = _build_key32(self.t["o_orderkey"],
+                                    self._cols["o_orderkey"].ptr)
+        self._ckey32 = _build_key32(self.t["o_custkey"],
+                                    self._cols["o_custkey"].ptr)
         if self._okey32 is not None:
             self.cstruct.o_orderkey32 = C.c_void_p(self._okey32.data_ptr())
         if self._ckey32 is not None:
@@ -196,12 +244,13 @@ class GpuOrders:
 class GpuCustomer:
     def __init__(self, n, device="cuda"):
         self.n = n
-        self.t = {
-            "c_custkey": torch.empty(n, dtype=torch.int64, device=device),
-            "c_mktsegment": torch.empty(n, dtype=torch.uint8, device=device),
+        self._cols = {
+            "c_custkey": _Col(n, torch.int64, device),
+            "c_mktsegment": _Col(n, torch.uint8, device),
         }
+        self.t = {k: c.t for k, c in self._cols.items()}
         self.cstruct = CustomerDev(
-            n=n, **{k: C.c_void_p(v.data_ptr()) for k, v in self.t.items()})
+            n=n, **{k: C.c_void_p(c.ptr) for k, c in self._cols.items()})
 
     @classmethod
     def generate(cls, n_global, rank=0, nranks=1, seed=SEED_DEFAULT):
@@ -211,6 +260,14 @@ class GpuCustomer:
              _stream())
         return t
 
+    @classmethod
+    def from_host(cls, cols):
+        """Stage a customer table from host columns (c_custkey,
+        c_mktsegment)."""
+        t = cls(len(cols["c_custkey"]))
+        _h2d_cols(t, cols)
+        return t
+
 
 class GpuPart:
     """Replicated dimension table (every rank holds all rows — the locator
@@ -218,18 +275,26 @@ class GpuPart:
 
     def __init__(self, n, device="cuda"):
         self.n = n
-        self.t = {
-            "p_partkey": torch.empty(n, dtype=torch.int64, device=device),
-            "p_type": torch.empty(n, dtype=torch.uint8, device=device),
+        self._cols = {
+            "p_partkey": _Col(n, torch.int64, device),
+            "p_type": _Col(n, torch.uint8, device),
         }
+        self.t = {k: c.t for k, c in self._cols.items()}
         self.cstruct = PartDev(
-            n=n, **{k: C.c_void_p(v.data_ptr()) for k, v in self.t.items()})
+            n=n, **{k: C.c_void_p(c.ptr) for k, c in self._cols.items()})
 
     @classmethod
     def generate(cls, n_global, seed=SEED_DEFAULT):
         t = cls(n_global)
         call("otbx_gen_part_dev", C.byref(t.cstruct), C.c_uint64(seed),
              C.c_int64(n_global), _stream())
+        return t
+
+    @classmethod
+    def from_host(cls, cols):
+        """Stage a part table from host columns (p_partkey, p_type)."""
+        t = cls(len(cols["p_partkey"]))
+        _h2d_cols(t, cols)
         return t
 
 
@@ -398,7 +463,15 @@ class GpuQ3Fragment(CustomScanState):
         ng = torch.zeros(1, dtype=torch.int64, device="cuda")
         stats = torch.zeros(1, dtype=torch.int64, device="cuda")
         ms = (C.c_float * 4)()
-        ck = C.c_void_p(self.cust_keys.data_ptr()) if self.cust_keys is not None else None
+        ck = None
+        if self.cust_keys is not None:
+            # an EMPTY broadcast (no customer in the segment anywhere) is
+            # still a broadcast: torch gives an empty tensor a NULL
+            # data_ptr, which the C-ABI would read as "filter the local
+            # customer table instead"
+            ck_buf = self.cust_keys if len(self.cust_keys) else \
+                torch.zeros(1, dtype=torch.int64, device="cuda")
+            ck = C.c_void_p(ck_buf.data_ptr())
         nck = C.c_int64(0 if self.cust_keys is None else len(self.cust_keys))
         call("otbx_q3_partial", C.byref(self.cu.cstruct), C.byref(self.od.cstruct),
              C.byref(self.li.cstruct), ck, nck, C.c_uint8(self.segment),

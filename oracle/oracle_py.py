@@ -197,6 +197,62 @@ def gen_tables(n_lineitem, rank=0, nranks=1, seed=42, need=("lineitem",),
     return out
 
 
+_NP_COLS = {
+    "lineitem": (_Lineitem, [
+        ("l_orderkey", np.int64, C.c_int64),
+        ("l_quantity", np.float64, C.c_double),
+        ("l_extendedprice", np.float64, C.c_double),
+        ("l_discount", np.float64, C.c_double),
+        ("l_tax", np.float64, C.c_double),
+        ("l_returnflag", np.uint8, C.c_uint8),
+        ("l_linestatus", np.uint8, C.c_uint8),
+        ("l_shipdate", np.int32, C.c_int32),
+        ("l_partkey", np.int64, C.c_int64)]),
+    "orders": (_Orders, [
+        ("o_orderkey", np.int64, C.c_int64),
+        ("o_custkey", np.int64, C.c_int64),
+        ("o_orderdate", np.int32, C.c_int32),
+        ("o_shippriority", np.int32, C.c_int32)]),
+    "customer": (_Customer, [
+        ("c_custkey", np.int64, C.c_int64),
+        ("c_mktsegment", np.uint8, C.c_uint8)]),
+    "part": (_Part, [
+        ("p_partkey", np.int64, C.c_int64),
+        ("p_type", np.uint8, C.c_uint8)]),
+}
+
+
+def tables_from_numpy(lineitem=None, orders=None, customer=None, part=None):
+    """Wrap caller-supplied columns (dicts of numpy arrays keyed by column
+    name) in the dict shape gen_tables returns, so q1/q3/q9_partial run on
+    hand-built tables unchanged. Each table's "struct" points into the
+    contiguous copies stored beside it, which keeps them alive. A lineitem
+    column that is left out reads as zeros (l_shipdate gives the row
+    count)."""
+    given = {"lineitem": lineitem, "orders": orders, "customer": customer,
+             "part": part}
+    out = {}
+    for name, cols in given.items():
+        if cols is None:
+            continue
+        ctype, spec = _NP_COLS[name]
+        first = "l_shipdate" if name == "lineitem" else spec[0][0]
+        n = len(cols[first])
+        t = ctype()
+        t.n = n
+        tab = {"struct": t}
+        for col, dt, ct in spec:
+            a = (np.ascontiguousarray(cols[col], dtype=dt) if col in cols
+                 else np.zeros(n, dtype=dt))
+            assert a.shape == (n,), (name, col, a.shape, n)
+            if a.size == 0:   # keep the C side off a dangling 0-length base
+                a = np.zeros(1, dtype=dt)[:0]
+            tab[col] = a
+            setattr(t, col, a.ctypes.data_as(C.POINTER(ct)))
+        out[name] = tab
+    return out
+
+
 def q1_partial(tables, cutoff=2436):
     L = lib()
     g = (OraQ1Group * 8)()
