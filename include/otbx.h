@@ -42,6 +42,10 @@
  *                            ExecWindowAgg (executor/nodeWindowAgg.c) with
  *                            row_number / rank / dense_rank and count / sum
  *                            over the default frame (windowfuncs.c:82-118)
+ *   otbx_group_agg         — the Agg node's sorted strategies over that
+ *                            sorted input: AGG_SORTED / AGG_PLAIN
+ *                            (agg_retrieve_direct, nodeAgg.c:2249) with
+ *                            several count / sum / min / max per group
  *   otbx_filter_sel        — ExecScan/ExecQual for any qual shape: a CNF of
  *                            typed, nullable comparisons (execScan.c:140,
  *                            EEOP_QUAL execExprInterp.c:919) → the ordered
@@ -748,6 +752,112 @@ otbx_status otbx_window(const otbx_sortspec *spec, int32_t npart,
                         const double *vals_dev, const uint8_t *val_null_dev,
                         void *ws_dev, size_t ws_bytes,
                         const otbx_window_out *out, void *stream);
+
+/* ---- GPU GroupAggregate: count / sum / min / max per run of equal keys ----
+ * The sorted-input aggregation strategy of the Agg node (AGG_SORTED, and
+ * AGG_PLAIN with no keys: agg_retrieve_direct, executor/nodeAgg.c:2249,
+ * advancing every aggregate of the target list per row, advance_aggregates
+ * :856). One call reduces every key run of the sorted input to ONE ROW PER
+ * GROUP for up to OTBX_MAX_AGGS aggregates at once; all outputs share the
+ * same group index, and groups come out in key order.
+ *
+ * GROUPING
+ *   - spec lists the GROUP BY keys (0..8), typed and flagged as for
+ *     otbx_sort_perm. Position j is input row perm_dev[j]; perm_dev == NULL
+ *     means identity (the columns are already in order). An entry outside
+ *     [0, n) is clamped, so it cannot address outside the columns.
+ *   - A new group starts at j = 0 and wherever row j differs from row j-1 on
+ *     any key. Equal means what otbx_sort_perm and otbx_window mean: NULL
+ *     equals NULL, every NaN equals every NaN, -0.0 == +0.0, the value
+ *     stored under a NULL is ignored (the test is made on the sort's own
+ *     normalised key).
+ *   - The caller guarantees that equal keys are adjacent: a perm from
+ *     otbx_sort_perm on these keys, or on a longer key list with these as
+ *     prefix, qualifies. This is not checked; non-adjacent equal keys form
+ *     separate groups, as the reference's GroupAggregate does on unsorted
+ *     input.
+ *   - Groups are emitted in position order: output g is the g-th key run.
+ *     first_row_dev[g] is the input row index of the group's first position
+ *     (the representative tuple, the row_idx convention of otbx_agg_i64n);
+ *     it feeds otbx_gather_* to materialise the key columns.
+ *   - naggs == 0 is legal: DISTINCT on the keys.
+ *   - nkeys == 0 is AGG_PLAIN: one group over all rows. With n == 0 it still
+ *     emits one row, as agg_retrieve_direct does for an empty input without
+ *     grouping columns: counts 0, SUM / MIN / MAX NULL, first_row = -1.
+ *   - nkeys > 0 and n == 0: *ngroups_dev = 0 and nothing else is written.
+ *
+ * AGGREGATES — all transition functions are strict: NULL inputs are skipped
+ * and the first non-NULL input becomes the state.
+ *   COUNT_STAR            int64 rows in the group           (int8inc :714)
+ *   COUNT      any type   int64 non-NULL rows; only the mask is read, and
+ *                         without a mask it equals COUNT_STAR (int8inc_any)
+ *   SUM   F64             double (float8pl, float.c:970); see NUMERICS
+ *   SUM   I32, U8         int64, exact (int4_sum, numeric.c:6154; cannot
+ *                         overflow for n <= INT32_MAX)
+ *   SUM   I64             exact int128: out = uint64 low word, out_hi =
+ *                         int64 high word (int8_sum / Int128AggState; the
+ *                         encoding of otbx_dec_group)
+ *   MIN / MAX I64,I32,U8  same type as the input (int8smaller / int8larger,
+ *                         int4larger)
+ *   MIN / MAX F64         double, the BIT PATTERN OF THE CHOSEN INPUT ROW
+ *                         (float8smaller / float8larger, float.c:839/853)
+ *   SUM / MIN / MAX of a group without a non-NULL input: out_null = 1 and
+ *   the value stored is 0.
+ *
+ * FLOAT MIN / MAX follow float8_cmp_internal: NaN is greater than
+ *   everything, +Inf included. On a tie the reference returns its second
+ *   argument, so THE LATER ROW IN POSITION ORDER WINS; this covers -0 / +0
+ *   and NaNs of different sign or payload and is reproduced bit for bit:
+ *   MAX of [+0.0, -0.0] is -0.0 and of [-0.0, +0.0] is +0.0; MAX of
+ *   [NaN(a), 1.0, NaN(b)] is NaN(b); MIN of [1.0, NaN] is 1.0; MIN of an
+ *   all-NaN group is its last NaN. ("Keep the left operand if it is strictly
+ *   greater — MIN: strictly smaller — else the right" is associative, so the
+ *   order-preserving tree reduction is exact.)
+ *
+ * NUMERICS OF SUM(F64): the clause of otbx_window's sum_v. The reduction is
+ *   SEGMENTED — nothing from one group ever reaches another, nothing is a
+ *   difference of prefix sums, and there are no float atomics. The identity
+ *   is -0.0. The association order is a tree: bit-equal to left-to-right
+ *   float8pl wherever every order is exact, and otherwise within
+ *   m*u*sum|x| / (1 - m*u), m = group rows - 1, u = 2^-53. Overflow of
+ *   finite inputs is not detected. The result is run-to-run deterministic:
+ *   the same call twice gives the same bits.
+ *
+ * Stream-ordered, no host synchronisation, nothing cached (otbx_finish has
+ * nothing to release); entries past *ngroups_dev are never written. Checked
+ * before any HIP call, each returning OTBX_ERR_INVALID: spec, aggs or
+ * ngroups_dev NULL; nkeys outside 0..8; naggs outside 0..8; a key type code
+ * outside 0..3 or key flags outside bits 0-1; func or type of an aggregate
+ * out of range; SUM / MIN / MAX with col == NULL and n > 0; out == NULL;
+ * out_null missing for SUM / MIN / MAX or present for a count; out_hi
+ * missing for SUM over I64 or present for anything else; naggs == 0 with
+ * first_row_dev == NULL (nothing requested); n < 0 or n > INT32_MAX; a NULL
+ * key column with n > 0; ws_bytes below otbx_group_agg_workspace_bytes(n),
+ * or ws_dev not 16-byte aligned. otbx_group_agg_workspace_bytes is pure host
+ * code and monotone in n. */
+enum { OTBX_AGG_COUNT_STAR = 0, OTBX_AGG_COUNT, OTBX_AGG_SUM,
+       OTBX_AGG_MIN, OTBX_AGG_MAX };
+#define OTBX_MAX_AGGS 8
+typedef struct {
+    const void    *col;      /* input column of `type`; ignored by COUNT_STAR / COUNT */
+    const uint8_t *nulls;    /* byte per row, nonzero = NULL; may be NULL              */
+    void          *out;      /* one entry per group, capacity n                        */
+    int64_t       *out_hi;   /* SUM over I64 only: high words of the int128 sum        */
+    uint8_t       *out_null; /* SUM / MIN / MAX: 1 where the group held no non-NULL
+                                input (value stored is 0); must be NULL for counts     */
+    int32_t        func;     /* OTBX_AGG_*                                             */
+    int32_t        type;     /* OTBX_SORT_I64 / F64 / I32 / U8                         */
+} otbx_aggcall;              /* 48 B */
+typedef struct { int32_t naggs; int32_t _pad; otbx_aggcall agg[OTBX_MAX_AGGS]; } otbx_aggcalls;
+
+otbx_status otbx_group_agg_workspace_bytes(int64_t n, size_t *bytes);
+otbx_status otbx_group_agg(const otbx_sortspec *spec,   /* the GROUP BY keys, 0..8 */
+                           const int64_t *perm_dev,     /* NULL = identity         */
+                           int64_t n, const otbx_aggcalls *aggs,
+                           void *ws_dev, size_t ws_bytes,
+                           int64_t *first_row_dev,      /* capacity n; may be NULL */
+                           int64_t *ngroups_dev,        /* int64[1], required      */
+                           void *stream);
 
 /* ---- generic GPU Filter: WHERE quals → ordered selection vector ----
  * The ExecScan / ExecQual analog (executor/execScan.c:140-363 over the

@@ -106,6 +106,28 @@ class WindowOutDev(C.Structure):
                 ("sum_isnull", C.c_void_p), ("part_rows", C.c_void_p)]
 
 
+AGG_FUNCS = {"count_star": 0, "count": 1, "sum": 2, "min": 3, "max": 4}
+MAX_AGGS = 8   # OTBX_MAX_AGGS
+
+
+class AggCallDev(C.Structure):
+    """otbx_aggcall (include/otbx.h): one aggregate of a GroupAggregate
+    target list, 48 bytes."""
+    _fields_ = [("col", C.c_void_p), ("nulls", C.c_void_p),
+                ("out", C.c_void_p), ("out_hi", C.c_void_p),
+                ("out_null", C.c_void_p),
+                ("func", C.c_int32), ("type", C.c_int32)]
+
+
+class AggCallsDev(C.Structure):
+    """otbx_aggcalls: up to 8 aggregates, 392 bytes."""
+    _fields_ = [("naggs", C.c_int32), ("_pad", C.c_int32),
+                ("agg", AggCallDev * MAX_AGGS)]
+
+
+assert C.sizeof(AggCallDev) == 48 and C.sizeof(AggCallsDev) == 392
+
+
 class QualTermDev(C.Structure):
     """otbx_qualterm (include/otbx.h): one comparison of a qual, 64 bytes."""
     _fields_ = [("col", C.c_void_p), ("nulls", C.c_void_p),
@@ -171,6 +193,7 @@ def lib():
         _lib.otbx_sort_workspace_bytes.argtypes = [i64, C.c_int32, i64, szp]
         _lib.otbx_window_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_filter_workspace_bytes.argtypes = [i64, szp]
+        _lib.otbx_group_agg_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_q1code_plan.argtypes = [
             C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
             C.POINTER(Q1CodeDesc), C.POINTER(C.c_int32)]
@@ -212,4 +235,5 @@ EXPORTED_SYMBOLS = [
     "otbx_window_workspace_bytes", "otbx_window",
     "otbx_filter_workspace_bytes", "otbx_filter_sel",
     "otbx_project",
+    "otbx_group_agg_workspace_bytes", "otbx_group_agg",
 ]

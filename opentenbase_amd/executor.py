@@ -16,9 +16,10 @@ import math
 
 import torch
 
-from ._lib import (CustomerDev, ExprDev, KeysetDev, LineitemDev, OrdersDev,
-                   OtbxError, PartDev, Q1_DICT_MAX, Q1CodeDesc, QualDev,
-                   SortSpecDev, WindowOutDev, call, check, lib)
+from ._lib import (AGG_FUNCS, MAX_AGGS, AggCallsDev, CustomerDev, ExprDev,
+                   KeysetDev, LineitemDev, OrdersDev, OtbxError, PartDev,
+                   Q1_DICT_MAX, Q1CodeDesc, QualDev, SortSpecDev,
+                   WindowOutDev, call, check, lib)
 
 Q1_SLOT_ORDER = [(b"A", b"F"), (b"A", b"O"), (b"N", b"F"),
                  (b"N", b"O"), (b"R", b"F"), (b"R", b"O")]
@@ -902,6 +903,193 @@ def cume_dist(count_star, part_rows):
     out = np.asarray(count_star, dtype=np.float64) / \
         np.asarray(part_rows, dtype=np.float64)
     return float(out) if out.ndim == 0 else out
+
+
+class GpuGroupAgg(CustomScanState):
+    """The Agg node's sorted strategies (AGG_SORTED; AGG_PLAIN with no keys:
+    agg_retrieve_direct, nodeAgg.c:2249) for a target list of up to 8
+    aggregates over 0..8 GROUP BY keys (device tensors of dtype int64,
+    float64, int32 or uint8, with optional null masks). aggs is a list of
+        ("count_star",) | ("count", col[, nulls])
+        | ("sum" | "min" | "max", col[, nulls])
+    Keys sort as GpuSort sorts them (descending / nulls_first / key_nulls).
+    Runs GpuSort on the keys — skipped with zero keys, or when a sorted
+    `perm` is passed — then otbx_group_agg. Yields ONE tuple, a dict:
+        "ngroups"   int
+        "first_row" int64 tensor: the input row of each group's first row
+        "keys"      [(values, nulls or None)] gathered through first_row by
+                    the native gather kernels
+        "aggs"      [(values, nulls or None)] cut to ngroups, in target-list
+                    order; an int64 SUM yields (lo, hi, nulls): the int128
+                    sum, see int128_sums()
+    Groups come out in key order. Contract in include/otbx.h
+    (otbx_group_agg); AVG is a finalizer: avg_f64 below, dec_avg for the
+    integer sums."""
+
+    def __init__(self, keys, aggs, descending=None, nulls_first=None,
+                 key_nulls=None, perm=None, n=None):
+        super().__init__()
+        self.keys = list(keys)
+        nk = len(self.keys)
+        if nk > 8:
+            raise OtbxError(3, "group agg: at most 8 keys")
+        self.nulls = [None] * nk if key_nulls is None else list(key_nulls)
+        if len(self.nulls) != nk:
+            raise OtbxError(3, "group agg: one key_nulls entry per key")
+        self.flags = sort_flags(nk, descending, nulls_first)
+        for k in self.keys:
+            if k.dtype not in _SORT_TYPE:
+                raise OtbxError(3, f"group agg: unsupported key dtype {k.dtype}")
+        self.aggs = []
+        for a in aggs:
+            a = tuple(a)
+            if not a or a[0] not in AGG_FUNCS:
+                raise OtbxError(3, f"group agg: unknown aggregate {a[:1]}")
+            func = a[0]
+            col = a[1] if len(a) > 1 else None
+            nl = a[2] if len(a) > 2 else None
+            if func in ("sum", "min", "max"):
+                if col is None:
+                    raise OtbxError(3, f"group agg: {func} needs a column")
+                if col.dtype not in _SORT_TYPE:
+                    raise OtbxError(
+                        3, f"group agg: unsupported dtype {col.dtype}")
+            self.aggs.append((func, col, nl))
+        if len(self.aggs) > MAX_AGGS:
+            raise OtbxError(3, "group agg: at most 8 aggregates")
+        if n is None:
+            cols = self.keys + [c for _, c, _ in self.aggs if c is not None]
+            if cols:
+                n = len(cols[0])
+            elif perm is not None:
+                n = len(perm)
+            else:
+                raise OtbxError(3, "group agg: no column to size by — pass n")
+        self.n = int(n)
+        for k in self.keys:
+            if len(k) != self.n:
+                raise OtbxError(3, "group agg: key columns differ in length")
+        self.perm = perm
+        self.sort_ms = None
+        self.group_agg_ms = None
+
+    def spec(self):
+        sp = SortSpecDev()
+        sp.nkeys = len(self.keys)
+        for c, k in enumerate(self.keys):
+            sp.key[c].col = k.data_ptr()
+            nt = self.nulls[c]
+            sp.key[c].nulls = nt.data_ptr() if nt is not None else None
+            sp.key[c].type = _SORT_TYPE[k.dtype]
+            sp.key[c].flags = self.flags[c]
+        return sp
+
+    def _run(self):
+        L = lib()
+        n = self.n
+        self.sort_ms = 0.0
+        perm = self.perm
+        if perm is None and self.keys:
+            srt = GpuSort(self.keys, nulls=self.nulls)
+            srt.flags = list(self.flags)
+            srt.BeginCustomScan()
+            perm = srt.ExecCustomScan()
+            srt.EndCustomScan()
+            self.sort_ms = srt.sort_ms
+        sp = self.spec()
+        ws_bytes = C.c_size_t(0)
+        check(L.otbx_group_agg_workspace_bytes(C.c_int64(n),
+                                               C.byref(ws_bytes)),
+              "otbx_group_agg_workspace_bytes")
+        ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8,
+                         device="cuda")
+        cap = max(n, 1)
+
+        def new(dtype):
+            return torch.empty(cap, dtype=dtype, device="cuda")
+
+        calls = AggCallsDev()
+        calls.naggs = len(self.aggs)
+        outs = []
+        for i, (func, col, nl) in enumerate(self.aggs):
+            ac = calls.agg[i]
+            ac.func = AGG_FUNCS[func]
+            ac.type = _SORT_TYPE[col.dtype] if col is not None else 0
+            ac.col = col.data_ptr() if col is not None and n > 0 else None
+            ac.nulls = nl.data_ptr() if nl is not None and n > 0 else None
+            if func in ("count_star", "count"):
+                o = (new(torch.int64),)
+            elif func == "sum" and col.dtype == torch.int64:
+                o = (new(torch.int64), new(torch.int64), new(torch.uint8))
+                ac.out_hi = o[1].data_ptr()
+            elif func == "sum":
+                o = (new(torch.float64 if col.dtype == torch.float64
+                         else torch.int64), new(torch.uint8))
+            else:
+                o = (new(col.dtype), new(torch.uint8))
+            ac.out = o[0].data_ptr()
+            if len(o) > 1:
+                ac.out_null = o[-1].data_ptr()
+            outs.append(o)
+        first = new(torch.int64)
+        ng = torch.zeros(1, dtype=torch.int64, device="cuda")
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        call("otbx_group_agg", C.byref(sp),
+             C.c_void_p(perm.data_ptr()) if perm is not None and n > 0
+             else None,
+             C.c_int64(n), C.byref(calls), C.c_void_p(ws.data_ptr()),
+             C.c_size_t(ws_bytes.value), C.c_void_p(first.data_ptr()),
+             C.c_void_p(ng.data_ptr()), _stream())
+        ev1.record()
+        ngroups = int(ng.cpu().item())
+        self.group_agg_ms = ev0.elapsed_time(ev1)
+        first = first[:ngroups]
+        keys = []
+        for k, m in zip(self.keys, self.nulls):
+            if ngroups == 0:
+                keys.append((k[:0], None if m is None else m[:0]))
+            else:
+                keys.append((gather(k, first),
+                             None if m is None else gather(m, first)))
+        return [{"ngroups": ngroups, "first_row": first, "keys": keys,
+                 "aggs": [tuple(t[:ngroups] for t in o) if len(o) > 1
+                          else (o[0][:ngroups], None) for o in outs]}]
+
+    def explain(self):
+        if self.group_agg_ms is None:
+            return None
+        return {"sort": self.sort_ms, "group_agg": self.group_agg_ms}
+
+
+def int128_sums(lo, hi, nulls=None):
+    """Python ints of an int64 SUM's (lo, hi) output — the Int128AggState
+    encoding of otbx_group_agg: unsigned low word, signed high word. None
+    where nulls is set. Tensors or numpy arrays in, a list out."""
+    import numpy as np
+
+    def host(a):
+        return a.cpu().numpy() if isinstance(a, torch.Tensor) else \
+            np.asarray(a)
+    lo, hi = host(lo), host(hi)
+    nl = [0] * len(lo) if nulls is None else host(nulls).tolist()
+    lo = lo.view(np.uint64) if lo.dtype == np.int64 else lo
+    return [None if z else (int(h) << 64) | int(l)
+            for l, h, z in zip(lo.tolist(), hi.tolist(), nl)]
+
+
+def avg_f64(sum_v, count):
+    """float8_avg (float.c:2949) over the SUM(F64) / COUNT outputs: Sx / N.
+    AVG over no non-NULL input is NULL: None for scalars, NaN in an array
+    result."""
+    import numpy as np
+    s = np.asarray(sum_v, dtype=np.float64)
+    c = np.asarray(count, dtype=np.float64)
+    if s.ndim == 0 and c.ndim == 0:
+        return None if c == 0.0 else float(s / c)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(c == 0.0, np.nan, s / np.where(c == 0.0, 1.0, c))
 
 
 CMP_OPS = {"=": 0, "<>": 1, "<": 2, "<=": 3, ">": 4, ">=": 5,

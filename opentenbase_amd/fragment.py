@@ -248,6 +248,156 @@ def merge_var_partials(rows):
     return list(out)
 
 
+def combine_group_partials(keys, key_nulls, flags, aggs):
+    """The Finalize step of merge_group_partials on the gathered stream
+    (host numpy; the inputs are group-sized). keys / key_nulls: the key
+    columns and masks of every rank's group rows, concatenated in rank
+    order; flags: the per-key OTBX_SORT_* words; aggs: one tuple per
+    aggregate,
+        ("count_star" | "count", val, None)
+        ("sum" | "min" | "max", val, null)     val typed as the node's output
+        ("sum128", lo, hi, null)               the int64 SUM's int128 state
+    Rows are ordered by key (stable: rank order inside equal keys) and
+    adjacent equal keys — equal under the sort's normalised key — are
+    combined left to right, NULL partials skipped: counts by int8pl, F64
+    sums by float8pl, integer sums exactly (int128 with carry), MIN / MAX
+    under the operator's comparator, the later rank winning a tie. Returns
+    (keys, key_nulls, aggs) of the combined rows; keys are those of each
+    group's first row."""
+    import numpy as np
+    keys = [np.asarray(k) for k in keys]
+    nk = len(keys)
+    n = len(keys[0]) if nk else (len(aggs[0][1]) if aggs else 0)
+    cols = []   # np.lexsort: LAST entry is the primary key
+    norm = []
+    for c in range(nk):
+        m = None if key_nulls[c] is None else np.asarray(key_nulls[c])
+        nd, k = _sort_norm_host(keys[c], flags[c], m)
+        norm.append((nd, k))
+    for nd, k in reversed(norm):
+        cols += [k, nd]
+    order = np.lexsort(cols) if cols else np.arange(n)
+    start = np.zeros(n, dtype=bool)
+    if n:
+        start[0] = True
+    for nd, k in norm:
+        nd, k = nd[order], k[order]
+        start[1:] |= (nd[1:] != nd[:-1]) | (k[1:] != k[:-1])
+    starts = np.flatnonzero(start)
+    ng = len(starts)
+    gid = np.cumsum(start) - 1
+    slot = np.arange(n) - starts[gid] if n else np.zeros(0, dtype=np.int64)
+    width = int(slot.max()) + 1 if n else 0
+
+    def fold(parts, null, step):
+        """left-to-right over each group's partials; parts: arrays in
+        gathered order. Returns (accumulators, isnull)."""
+        parts = [np.asarray(p)[order] for p in parts]
+        live = np.ones(n, dtype=bool) if null is None else \
+            np.asarray(null)[order] == 0
+        acc = [np.zeros(ng, dtype=p.dtype) for p in parts]
+        has = np.zeros(ng, dtype=bool)
+        for s in range(width):
+            rows = np.flatnonzero((slot == s) & live)
+            g = gid[rows]
+            new = [p[rows] for p in parts]
+            old = [a[g] for a in acc]
+            both = has[g]
+            res = step(old, new)
+            for a, r, x in zip(acc, res, new):
+                a[g] = np.where(both, r, x)
+            has[g] = True
+        return acc, (~has).astype(np.uint8)
+
+    u64 = np.uint64
+
+    def add(old, new):
+        with np.errstate(invalid="ignore", over="ignore"):
+            return [old[0] + new[0]]
+
+    def add128(old, new):
+        lo = old[0] + new[0]                       # uint64, wraps
+        carry = (lo < old[0]).astype(np.int64)
+        with np.errstate(over="ignore"):
+            return [lo, old[1] + new[1] + carry]
+
+    def pick(is_max):
+        def step(old, new):
+            a = _sort_norm_host(old[0], 0, None)[1]
+            b = _sort_norm_host(new[0], 0, None)[1]
+            keep = a > b if is_max else a < b      # strictly: a tie → later
+            return [np.where(keep, old[0], new[0])]
+        return step
+
+    out = []
+    for a in aggs:
+        func = a[0]
+        if func in ("count_star", "count"):
+            acc, _ = fold([np.asarray(a[1]).astype(np.int64)], None, add)
+            out.append((acc[0], None))
+        elif func == "sum128":
+            lo = np.asarray(a[1])
+            lo = lo.view(u64) if lo.dtype == np.int64 else lo.astype(u64)
+            acc, isnull = fold([lo, np.asarray(a[2]).astype(np.int64)], a[3],
+                               add128)
+            out.append((acc[0], acc[1], isnull))
+        elif func == "sum":
+            acc, isnull = fold([a[1]], a[2], add)
+            out.append((acc[0], isnull))
+        elif func in ("min", "max"):
+            acc, isnull = fold([a[1]], a[2], pick(func == "max"))
+            out.append((acc[0], isnull))
+        else:
+            raise OtbxError(3, f"merge_group_partials: unknown aggregate "
+                               f"{func}")
+    first = order[starts] if n else order[:0]
+    return ([k[first] for k in keys],
+            [None if m is None else np.asarray(m)[first] for m in key_nulls],
+            out)
+
+
+def merge_group_partials(keys, aggs, key_nulls=None, descending=None,
+                         nulls_first=None):
+    """Coordinator combine of a GpuGroupAgg (the Finalize Aggregate above
+    the gathered Partial GroupAggregate rows): every rank passes its group
+    rows — key columns, optional key masks, and per aggregate the tuple
+    combine_group_partials describes (tensors or numpy arrays; an int64 SUM
+    as ("sum128", lo, hi, null)). The rows are all-gathered in rank order
+    with allgather_variable, ordered by key with the sort's own normalised
+    key and combined by combine_group_partials. Host-side numpy, as
+    merge_var_partials: the inputs are group-sized. Returns (keys,
+    key_nulls, aggs) as numpy arrays in key order. With one rank or no
+    process group the input is returned unchanged. All ranks must pass the
+    same columns (a mask on one rank = on every rank)."""
+    from . import executor as ex
+    import numpy as np
+    nk = len(keys)
+    key_nulls = [None] * nk if key_nulls is None else list(key_nulls)
+    flags = ex.sort_flags(nk, descending, nulls_first)
+    if not is_dist() or dist.get_world_size() == 1:
+        return keys, key_nulls, aggs
+    dev = "cuda" if torch.cuda.is_available() and \
+        dist.get_backend() == "nccl" else "cpu"
+
+    def gathered(a):
+        if a is None:
+            return None
+        if not isinstance(a, torch.Tensor):
+            a = np.ascontiguousarray(a)
+            dt = a.dtype
+            if dt == np.uint64:                    # torch moves it as int64
+                a = a.view(np.int64)
+            out = allgather_variable(torch.from_numpy(a).to(dev))
+            out = out.cpu().numpy()
+            return out.view(np.uint64) if dt == np.uint64 else out
+        return allgather_variable(a.to(dev)).cpu().numpy()
+
+    gk = [gathered(k) for k in keys]
+    gn = [gathered(m) for m in key_nulls]
+    ga = [(a[0],) + tuple(gathered(x) for x in a[1:]) for a in aggs]
+    return combine_group_partials(gk, gn, flags, ga)
+
+
 def finalize_q1(rows):
     return q1_finalize(rows)
 

@@ -25,6 +25,12 @@ distinct from the fused query pipelines.
                                    plain-torch composition of the same
                                    expressions (writes
                                    profiles/project_ops.txt, or PATH)
+  generic_ops_bench.py --groupagg [--rows N] [--out PATH]
+                                   otbx_group_agg at 600 M rows (or N) and
+                                   4 / 1 M / 100 M groups, timed apart from
+                                   its sort, next to otbx_window, the hash
+                                   aggregate and a plain-torch composition
+                                   (writes profiles/groupagg_ops.txt, or PATH)
 """
 import ctypes as C
 import os
@@ -35,7 +41,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from opentenbase_amd import executor as ex  # noqa: E402
-from opentenbase_amd._lib import WindowOutDev, call, lib  # noqa: E402
+from opentenbase_amd._lib import (AGG_FUNCS, AggCallsDev,  # noqa: E402
+                                  WindowOutDev, call, lib)
 
 
 def bench_agg(n, ngroups):
@@ -513,6 +520,204 @@ def bench_window(out_path):
         f.write("\n".join(lines) + "\n")
 
 
+class _GroupAggCall:
+    """otbx_group_agg on an already sorted permutation, buffers allocated
+    once. aggs: [(func, col or None)] without masks."""
+
+    def __init__(self, srt, aggs):
+        self.n = srt.n
+        self.spec, self.perm, self.stream = srt.spec, srt.perm, srt.stream
+        wsb = C.c_size_t(0)
+        lib().otbx_group_agg_workspace_bytes(C.c_int64(self.n), C.byref(wsb))
+        self.wsb = wsb.value
+        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device="cuda")
+        self.calls = AggCallsDev()
+        self.calls.naggs = len(aggs)
+        self.outs = []
+        self.row_bytes, self.group_bytes = 0, 8          # first_row
+        for i, (func, col) in enumerate(aggs):
+            ac = self.calls.agg[i]
+            ac.func = AGG_FUNCS[func]
+            ac.type = ex._SORT_TYPE[col.dtype] if col is not None else 0
+            ac.col = col.data_ptr() if col is not None else None
+            wide = func == "sum" and col.dtype == torch.int64
+            dt = torch.int64 if func in ("count_star", "count") or wide \
+                else col.dtype
+            o = [torch.empty(self.n, dtype=dt, device="cuda")]
+            ac.out = o[0].data_ptr()
+            if wide:
+                o.append(torch.empty(self.n, dtype=torch.int64, device="cuda"))
+                ac.out_hi = o[1].data_ptr()
+            if func not in ("count_star", "count"):
+                o.append(torch.empty(self.n, dtype=torch.uint8, device="cuda"))
+                ac.out_null = o[-1].data_ptr()
+            self.outs.append(o)
+            # per aggregate and row: flag byte, perm, the value
+            self.row_bytes += 1 + 8 + (col.element_size()
+                                       if func not in ("count_star", "count")
+                                       else 0)
+            self.group_bytes += sum(t.element_size() for t in o)
+        self.first = torch.empty(self.n, dtype=torch.int64, device="cuda")
+        self.ng = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+    def __call__(self):
+        call("otbx_group_agg", C.byref(self.spec),
+             C.c_void_p(self.perm.data_ptr()) if self.perm is not None
+             else None, C.c_int64(self.n), C.byref(self.calls),
+             C.c_void_p(self.ws.data_ptr()), C.c_size_t(self.wsb),
+             C.c_void_p(self.first.data_ptr()),
+             C.c_void_p(self.ng.data_ptr()), self.stream)
+
+    def algorithmic_bytes(self, key_bytes, ngroups):
+        """the boundary pass reads perm and gathers the keys
+        once and writes one flag byte; first_row reads the flags; every
+        aggregate reads flags and perm and gathers its value once; per group
+        first_row and each output are written once"""
+        per_row = 8 + key_bytes + 1 + 1 + self.row_bytes
+        return self.n * per_row + ngroups * self.group_bytes
+
+
+def _torch_group_sum(key, vals, perm):
+    """what a caller would write without the operator: gather,
+    unique_consecutive, segment_reduce"""
+    sk, sv = key[perm], vals[perm]
+    uk, counts = torch.unique_consecutive(sk, return_counts=True)
+    sums = torch.segment_reduce(sv, "sum", lengths=counts)
+    return uk, counts, sums
+
+
+def _exact_group_sum(key, v64, perm):
+    """counts and sums per key run from an int64 prefix sum: exact, and
+    independent of both the operator and torch.segment_reduce"""
+    n = len(perm)
+    sk = key[perm]
+    st = torch.ones(n, dtype=torch.bool, device="cuda")
+    st[1:] = sk[1:] != sk[:-1]
+    del sk
+    starts = st.nonzero().flatten()
+    del st
+    ends = torch.cat([starts[1:], torch.tensor([n], device="cuda")])
+    tot = torch.cumsum(v64[perm], 0)[ends - 1]
+    sums = tot.clone()
+    sums[1:] -= tot[:-1]
+    return ends - starts, sums.to(torch.float64)
+
+
+def bench_groupagg(out_path, n=600_000_000):
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    say("# tools/generic_ops_bench.py --groupagg — best / worst of 5 wall "
+        "time after torch.cuda.synchronize(), columns staged")
+    say("# GROUP BY one i64 key; the sort and otbx_group_agg are timed apart; "
+        "set A = {count_star, sum f64}, set B = {count_star, sum f64, "
+        "min f64, max f64, sum i64}")
+    g = torch.Generator(device="cuda").manual_seed(11)
+    v64 = torch.randint(-1000, 1001, (n,), dtype=torch.int64, device="cuda",
+                        generator=g)
+    vals = v64.to(torch.float64)
+    ivals = torch.randint(-2**40, 2**40, (n,), dtype=torch.int64,
+                          device="cuda", generator=g)
+    set_a = [("count_star", None), ("sum", vals)]
+    set_b = set_a + [("min", vals), ("max", vals), ("sum", ivals)]
+    for groups in (4, 1_000_000, 100_000_000):
+        key = torch.randint(0, groups, (n,), dtype=torch.int64, device="cuda",
+                            generator=g)
+        srt = _SortCall([key], [False])
+        sb, sw = _best_of_5(srt)
+        say(f"groups={groups:_} n={n:_}: sort best {sb*1e3:8.2f} ms  worst "
+            f"{sw*1e3:8.2f} ms")
+        res = {}
+        for tag, aggs in (("A", set_a), ("B", set_b)):
+            ga = _GroupAggCall(srt, aggs)
+            gb, gw = _best_of_5(ga)
+            ng = int(ga.ng.cpu().item())
+            nbytes = ga.algorithmic_bytes(8, ng)
+            tbs = nbytes / gb / 1e12
+            say(f"  set {tag}: otbx_group_agg best {gb*1e3:8.2f} ms  worst "
+                f"{gw*1e3:8.2f} ms (spread {(gw-gb)/gb*100:.1f} %)  ngroups="
+                f"{ng:_}  {nbytes/1e9:.1f} GB algorithmic  {tbs:5.2f} TB/s = "
+                f"{tbs*1e12/COPY_CEILING*100:4.1f} % of the 6.29 TB/s copy "
+                f"ceiling")
+            res[tag] = (gb, ga.outs[0][0][:ng].clone(),
+                        ga.outs[1][0][:ng].clone())
+            del ga
+            torch.cuda.empty_cache()
+        ga_best, ga_cnt, ga_sum = res["A"]
+        xc, xs = _exact_group_sum(key, v64, srt.perm)
+        say(f"  set A equals the exact int64 prefix-sum reference: counts "
+            f"{bool(torch.equal(xc, ga_cnt))}, sums "
+            f"{bool(torch.equal(xs, ga_sum))}")
+        # (a) otbx_window asked for the same numbers at every row
+        win = _WindowCall(srt, 1, vals, ("count_star", "sum_v"))
+        wb, ww = _best_of_5(win)
+        say(f"  (a) otbx_window count_star + sum_v, npart == nkeys: best "
+            f"{wb*1e3:8.2f} ms  worst {ww*1e3:8.2f} ms; window / group_agg "
+            f"(set A) time ratio: {wb/ga_best:.2f}")
+        del win
+        torch.cuda.empty_cache()
+        # (b) the hash path end to end against sort + group_agg
+        hb = bench_agg_on(key, vals)
+        say(f"  (b) otbx_agg_i64 (hash) best {hb*1e3:8.2f} ms; sort + "
+            f"group_agg (set A) {(sb+ga_best)*1e3:8.2f} ms; ratio sorted / "
+            f"hash: {(sb+ga_best)/hb:.2f}")
+        torch.cuda.empty_cache()
+        # (c) plain torch on the same sorted permutation
+        try:
+            tb, tw = _best_of_5(lambda: _torch_group_sum(key, vals, srt.perm))
+            uk, counts, sums = _torch_group_sum(key, vals, srt.perm)
+            say(f"  (c) plain torch (gather, unique_consecutive, "
+                f"segment_reduce): best {tb*1e3:8.2f} ms  worst "
+                f"{tw*1e3:8.2f} ms; torch / group_agg (set A) time ratio: "
+                f"{tb/ga_best:.2f}; torch equals the exact reference: counts "
+                f"{bool(torch.equal(counts, xc))}, sums "
+                f"{bool(torch.equal(sums, xs))} ("
+                f"{int((sums != xs).sum().item()):_} sums differ)")
+            del uk, counts, sums
+        except RuntimeError as e:
+            say(f"  (c) plain torch composition failed: {str(e)[:120]}")
+        # the same call on pre-gathered columns with perm = NULL: what is
+        # left when the loads through perm are sequential instead
+        class _Sorted:
+            pass
+        pre = _Sorted()
+        pre.keys = [key[srt.perm]]
+        pv = vals[srt.perm]
+        pre.n, pre.perm, pre.stream = n, None, srt.stream
+        pre.spec = ex.GpuSort(pre.keys).spec()
+        ga = _GroupAggCall(pre, [("count_star", None), ("sum", pv)])
+        ib, iw = _best_of_5(ga)
+        say(f"  (d) set A, columns pre-gathered, perm = NULL: best "
+            f"{ib*1e3:8.2f} ms  worst {iw*1e3:8.2f} ms; the gathers through "
+            f"perm cost {(ga_best-ib)*1e3:.2f} ms of set A")
+        del ga, pre, pv, srt, key, res, ga_cnt, ga_sum, xc, xs
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def bench_agg_on(keys, vals):
+    """otbx_agg_i64 on given columns, best of 5 after a warm-up (seconds)"""
+    n = len(keys)
+    ws_bytes = C.c_size_t(0)
+    lib().otbx_agg_i64_workspace_bytes(C.c_int64(n), C.byref(ws_bytes))
+    ws = torch.empty(ws_bytes.value, dtype=torch.uint8, device="cuda")
+    out = torch.empty(n * 40, dtype=torch.uint8, device="cuda")
+    ng = torch.zeros(1, dtype=torch.int64, device="cuda")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def run():
+        call("otbx_agg_i64", C.c_void_p(keys.data_ptr()), None,
+             C.c_void_p(vals.data_ptr()), None, C.c_int64(n),
+             C.c_void_p(ws.data_ptr()), C.c_size_t(ws_bytes.value),
+             C.c_void_p(out.data_ptr()), C.c_void_p(ng.data_ptr()), stream)
+    return _best_of_5(run)[0]
+
+
 class _FilterCall:
     """otbx_filter_sel with everything preallocated; clauses as GpuFilter
     takes them"""
@@ -822,6 +1027,16 @@ if __name__ == "__main__":
         if "--out" in sys.argv:
             out_path = sys.argv[sys.argv.index("--out") + 1]
         bench_filter(out_path)
+        sys.exit(0)
+    if "--groupagg" in sys.argv:
+        repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        out_path = os.path.join(repo, "profiles", "groupagg_ops.txt")
+        if "--out" in sys.argv:
+            out_path = sys.argv[sys.argv.index("--out") + 1]
+        rows = 600_000_000
+        if "--rows" in sys.argv:
+            rows = int(sys.argv[sys.argv.index("--rows") + 1])
+        bench_groupagg(out_path, rows)
         sys.exit(0)
     if "--window" in sys.argv:
         repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
