@@ -97,6 +97,13 @@
  *                            parity-tested for future shapes). Affects
  *                            otbx_join_ext_workspace_bytes AND the route
  *                            identically (query sizing under the same env)
+ *   OTBX_TEXT_STAGE=0      — otbx_text_pred reads every row straight from
+ *                            global memory instead of staging a tile's
+ *                            bytes in LDS; =1 stages wherever a tile's
+ *                            offsets allow it. Unset: staged only for a
+ *                            LIKE with a % before the pattern's last token,
+ *                            the shapes where staging measured faster
+ *                            (tests run both paths; A/B)
  */
 #ifndef OTBX_H
 #define OTBX_H
@@ -1061,6 +1068,132 @@ otbx_status otbx_project(const otbx_expr *e,
                          void *out_dev, uint8_t *out_null_dev,
                          int64_t *err_dev,        /* int64[1], required       */
                          void *stream);
+
+/* ---- GPU text columns: LIKE / compare predicates and text gather ----
+ * A text column is variable-width: row i is bytes[offs[i] .. offs[i+1]).
+ * offs[0] need not be 0, so offs[a : b+1] over the same bytes is a valid
+ * column (a slice costs nothing). Every offset a kernel reads is clamped
+ * into [0, nbytes] and a negative length reads as 0, so broken offsets can
+ * never address outside bytes — the policy the other operators apply to
+ * perm and sel entries. The bytes under a NULL are never read for their
+ * value. sizeof(otbx_textcol) == 32.
+ *
+ * otbx_text_pred evaluates ONE predicate per call into a uint8 0 / 1
+ * column plus null mask — the operand types a U8 otbx_qualterm (b = 1) and
+ * Project's COL take, so a text qual flows into otbx_filter_sel without a
+ * text term in the pinned otbx_qualterm. Every function is strict: a NULL
+ * operand gives NULL, the value stored under a NULL is 0. out_null_dev may
+ * be NULL only when no operand carries a mask. With sel_dev, output row j
+ * is evaluated on source row sel_dev[j], clamped into [0, n_src); rows the
+ * selection leaves out are never read.
+ *
+ * The right operand is either the column *right (the six comparisons only;
+ * `right` is a host pointer, read during the call) or the constant
+ * cbytes[0 .. clen), at most OTBX_MAX_TEXT_CONST bytes; it travels in the
+ * launch arguments by value.
+ *   LIKE / NLIKE     textlike / textnlike (utils/adt/like.c:269,290) over
+ *                    MatchText (like_match.c:78): % any sequence, _ one
+ *                    character, \ makes the next pattern byte literal, the
+ *                    empty pattern matches only the empty text, everything
+ *                    else compares bytewise (no case folding; no ILIKE).
+ *                    `encoding` decides how _ and the restart after a %
+ *                    advance: OTBX_TEXT_SB one byte (SB_MatchText),
+ *                    OTBX_TEXT_UTF8 the fast NextChar (like.c:142): one
+ *                    byte, then every following byte with
+ *                    (b & 0xC0) == 0x80. The UTF-8 is not validated;
+ *                    invalid sequences match exactly as that macro makes
+ *                    them. The pattern is parsed on the host, before any
+ *                    HIP call, into literal / any-character / any-sequence
+ *                    tokens, a run of % and _ collapsed to "k characters,
+ *                    then any sequence" (like_match.c:128-144); the kernel
+ *                    matches iteratively with two cursors and one restart
+ *                    point (the position after the last %, advanced by one
+ *                    CHARACTER on a mismatch) — the same language as the
+ *                    reference's recursion, O(text × pattern), no stack.
+ *                    A pattern whose last byte is an unescaped \ is refused
+ *                    with OTBX_ERR_INVALID at call time. The reference
+ *                    raises "LIKE pattern must not end with escape
+ *                    character" only on rows whose match reaches that byte;
+ *                    refusing always is stricter and data-independent. The
+ *                    ESCAPE clause is host work (do_like_escape,
+ *                    like_match.c:247; executor.like_escape).
+ *   EQ NE LT LE GT GE  texteq / textne / text_lt … (varlena.c:1874-1998)
+ *                    under C collation (varstr_cmp with lc_collate_is_c,
+ *                    varlena.c:1624-1629): memcmp over the common prefix,
+ *                    bytes as UNSIGNED, then the shorter string is smaller.
+ *                    EQ / NE decide on the lengths first, as texteq does.
+ *                    Other collations are not supported.
+ * Stream-ordered, no workspace, no host synchronisation, nothing cached.
+ * Checked before any HIP call, each returning OTBX_ERR_INVALID: p NULL;
+ * out_dev NULL with n > 0; op or encoding out of range; a right column with
+ * LIKE / NLIKE or with clen != 0; clen outside 0..256; a trailing lone
+ * escape; n < 0, n > INT32_MAX, n_src < 0, n > n_src without sel_dev, n > 0
+ * with n_src == 0; bytes NULL with nbytes > 0; offs NULL with n_src > 0;
+ * nbytes < 0; out_null_dev NULL although an operand has a mask. n == 0 is
+ * valid and writes nothing. sizeof(otbx_textpred) == 312.
+ *
+ * TEXT GATHER applies a selection or permutation: dst row j = src row
+ * perm[j], entries clamped into [0, n_src); perm need not be a permutation
+ * (join output repeats rows). Two calls, because the caller must size the
+ * destination in between:
+ *   otbx_text_gather_offsets  dst_offs[0] = 0, dst_offs[j+1] = dst_offs[j]
+ *                    + len(perm[j]); dst_offs[n] is the total, the one
+ *                    value the caller reads back (the one synchronisation,
+ *                    where the Filter's caller reads its count). Tile sums
+ *                    → single-workgroup scan → apply; no inter-workgroup
+ *                    waiting. ws_dev: 8-byte aligned, at least
+ *                    otbx_text_gather_workspace_bytes(n).
+ *   otbx_text_gather_bytes    copies the bytes, balanced over OUTPUT BYTES:
+ *                    each workgroup owns a fixed slice of dst_bytes and
+ *                    finds its rows by binary search in dst_offs, so one
+ *                    1 MiB row among short ones is copied by many
+ *                    workgroups. dst_nbytes below dst_offs[n] truncates the
+ *                    writes and never overruns; dst_offs that were not made
+ *                    for this src and perm can give wrong bytes but never
+ *                    an access outside src->bytes or dst_bytes.
+ * The null mask travels by otbx_gather_u8. OTBX_ERR_INVALID before any HIP
+ * call: src, dst_offs_dev or (n > 0) perm_dev NULL; n < 0, n > INT32_MAX,
+ * n_src < 0, n > 0 with n_src == 0; the column checks above; a workspace
+ * that is short, NULL when bytes are needed or not 8-byte aligned;
+ * dst_nbytes < 0; dst_bytes_dev NULL with dst_nbytes > 0. */
+enum { OTBX_TXT_LIKE = 0, OTBX_TXT_NLIKE, OTBX_TXT_EQ, OTBX_TXT_NE,
+       OTBX_TXT_LT, OTBX_TXT_LE, OTBX_TXT_GT, OTBX_TXT_GE };
+enum { OTBX_TEXT_SB = 0, OTBX_TEXT_UTF8 = 1 };
+#define OTBX_MAX_TEXT_CONST 256
+typedef struct {
+    const uint8_t *bytes;   /* device, nbytes bytes, any alignment            */
+    const int64_t *offs;    /* device, n+1 non-decreasing byte offsets        */
+    const uint8_t *nulls;   /* byte per row, nonzero = NULL; may be NULL      */
+    int64_t        nbytes;  /* size of bytes[]                                 */
+} otbx_textcol;
+typedef struct {
+    otbx_textcol        left;
+    const otbx_textcol *right;     /* host pointer; NULL = use the constant   */
+    int32_t             op;        /* OTBX_TXT_*                              */
+    int32_t             encoding;  /* OTBX_TEXT_*                             */
+    int32_t             clen;      /* constant length, 0..256; 0 with right   */
+    int32_t             _pad;
+    uint8_t             cbytes[OTBX_MAX_TEXT_CONST];
+} otbx_textpred;
+
+otbx_status otbx_text_pred(const otbx_textpred *p,
+                           const int64_t *sel_dev,  /* NULL = identity        */
+                           int64_t n,      /* output rows (= len(sel) if given) */
+                           int64_t n_src,  /* rows in the columns             */
+                           uint8_t *out_dev, uint8_t *out_null_dev,
+                           void *stream);
+
+otbx_status otbx_text_gather_workspace_bytes(int64_t n, size_t *bytes);
+otbx_status otbx_text_gather_offsets(const otbx_textcol *src, int64_t n_src,
+                                     const int64_t *perm_dev, int64_t n,
+                                     void *ws_dev, size_t ws_bytes,
+                                     int64_t *dst_offs_dev /* n+1 */,
+                                     void *stream);
+otbx_status otbx_text_gather_bytes(const otbx_textcol *src, int64_t n_src,
+                                   const int64_t *perm_dev, int64_t n,
+                                   const int64_t *dst_offs_dev,
+                                   uint8_t *dst_bytes_dev, int64_t dst_nbytes,
+                                   void *stream);
 
 /* ---- repartition exchange ----
  * The GPU half of the reference's "Distribute results by H: col" exchange

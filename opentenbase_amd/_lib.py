@@ -156,6 +156,30 @@ class ExprDev(C.Structure):
                 ("instr", ExprInstrDev * 32)]
 
 
+TXT_OPS = {"like": 0, "not like": 1, "=": 2, "<>": 3, "<": 4, "<=": 5,
+           ">": 6, ">=": 7}                  # OTBX_TXT_*
+TEXT_ENCODINGS = {"sb": 0, "utf8": 1}        # OTBX_TEXT_*
+MAX_TEXT_CONST = 256                         # OTBX_MAX_TEXT_CONST
+
+
+class TextColDev(C.Structure):
+    """otbx_textcol (include/otbx.h): a variable-width text column, 32 B."""
+    _fields_ = [("bytes", C.c_void_p), ("offs", C.c_void_p),
+                ("nulls", C.c_void_p), ("nbytes", C.c_int64)]
+
+
+class TextPredDev(C.Structure):
+    """otbx_textpred: one text predicate, 312 bytes. `right` is a host
+    pointer to a TextColDev (keep that object alive over the call)."""
+    _fields_ = [("left", TextColDev), ("right", C.POINTER(TextColDev)),
+                ("op", C.c_int32), ("encoding", C.c_int32),
+                ("clen", C.c_int32), ("_pad", C.c_int32),
+                ("cbytes", C.c_uint8 * MAX_TEXT_CONST)]
+
+
+assert C.sizeof(TextColDev) == 32 and C.sizeof(TextPredDev) == 312
+
+
 class PartDev(C.Structure):
     _fields_ = [
         ("n", C.c_int64),
@@ -194,6 +218,7 @@ def lib():
         _lib.otbx_window_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_filter_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_group_agg_workspace_bytes.argtypes = [i64, szp]
+        _lib.otbx_text_gather_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_q1code_plan.argtypes = [
             C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
             C.POINTER(Q1CodeDesc), C.POINTER(C.c_int32)]
@@ -236,4 +261,6 @@ EXPORTED_SYMBOLS = [
     "otbx_filter_workspace_bytes", "otbx_filter_sel",
     "otbx_project",
     "otbx_group_agg_workspace_bytes", "otbx_group_agg",
+    "otbx_text_pred", "otbx_text_gather_workspace_bytes",
+    "otbx_text_gather_offsets", "otbx_text_gather_bytes",
 ]

@@ -16,9 +16,10 @@ import math
 
 import torch
 
-from ._lib import (AGG_FUNCS, MAX_AGGS, AggCallsDev, CustomerDev, ExprDev,
-                   KeysetDev, LineitemDev, OrdersDev, OtbxError, PartDev,
-                   Q1_DICT_MAX, Q1CodeDesc, QualDev, SortSpecDev,
+from ._lib import (AGG_FUNCS, MAX_AGGS, MAX_TEXT_CONST, TEXT_ENCODINGS,
+                   TXT_OPS, AggCallsDev, CustomerDev, ExprDev, KeysetDev,
+                   LineitemDev, OrdersDev, OtbxError, PartDev, Q1_DICT_MAX,
+                   Q1CodeDesc, QualDev, SortSpecDev, TextColDev, TextPredDev,
                    WindowOutDev, call, check, lib)
 
 Q1_SLOT_ORDER = [(b"A", b"F"), (b"A", b"O"), (b"N", b"F"),
@@ -1588,6 +1589,289 @@ class GpuProject(CustomScanState):
         if self.project_ms is None:
             return None
         return {"project": self.project_ms}
+
+
+# ---------------- text columns: LIKE / compare predicates, gather ----------
+
+TEXT_TILE = 256           # rows per workgroup of otbx_text_pred
+TEXT_LDS_BUDGET = 32768   # largest tile byte span the predicate stages in LDS
+TEXT_GATHER_CHUNK = 256 * 1024   # rows per pass of the gather's offset scan
+
+
+def _text_bytes(v, what):
+    if isinstance(v, str):
+        return v.encode("utf-8")
+    if isinstance(v, (bytes, bytearray)):
+        return bytes(v)
+    raise OtbxError(3, f"text: {what} is bytes or str, not {type(v).__name__}")
+
+
+def like_escape(pattern, esc):
+    """pattern LIKE ... ESCAPE esc → the equivalent pattern in the backslash
+    convention (do_like_escape, like_match.c:247). An empty esc means no
+    escape character: backslashes are doubled. esc == '\\' returns the
+    pattern as it is. An esc longer than one character (UTF-8) is an error.
+    Returns bytes."""
+    p = _text_bytes(pattern, "a pattern")
+    e = _text_bytes(esc, "an escape")
+    if len(e) == 0:
+        return p.replace(b"\\", b"\\\\")
+
+    def next_char(b, i):
+        i += 1
+        while i < len(b) and (b[i] & 0xC0) == 0x80:
+            i += 1
+        return i
+
+    if next_char(e, 0) != len(e):
+        raise OtbxError(3, "invalid escape string: must be empty or one "
+                           "character")
+    if e == b"\\":
+        return p
+    out = bytearray()
+    i, after = 0, False
+    while i < len(p):
+        j = next_char(p, i)
+        if p[i:j] == e and not after:
+            out += b"\\"
+            after = True
+        elif p[i] == 0x5C:
+            out += b"\\" if after else b"\\\\"
+            after = False
+        else:
+            out += p[i:j]
+            after = False
+        i = j
+    return bytes(out)
+
+
+class GpuText:
+    """A variable-width text column on the device (otbx_textcol): `bytes`
+    (uint8), `offs` (int64, n + 1 byte offsets; row i is
+    bytes[offs[i]:offs[i+1]]) and `nulls` (uint8, nonzero = NULL, or None).
+    GpuText(values) stages a list of bytes / str (UTF-8 encoded) / None;
+    GpuText(bytes=, offs=, nulls=) adopts existing tensors, so offs[a:b+1]
+    over the same bytes is a free slice."""
+
+    def __init__(self, values=None, *, bytes=None, offs=None, nulls=None):
+        if values is not None:
+            if bytes is not None or offs is not None or nulls is not None:
+                raise OtbxError(3, "text: values or tensors, not both")
+            import numpy as np
+            rows = [b"" if v is None else _text_bytes(v, "a value")
+                    for v in values]
+            lens = np.fromiter((len(r) for r in rows), dtype=np.int64,
+                               count=len(rows))
+            o = np.zeros(len(rows) + 1, dtype=np.int64)
+            np.cumsum(lens, out=o[1:])
+            flat = np.frombuffer(b"".join(rows), dtype=np.uint8)
+            bytes = torch.from_numpy(flat.copy()).cuda()
+            offs = torch.from_numpy(o).cuda()
+            if any(v is None for v in values):
+                m = np.fromiter((v is None for v in values), dtype=np.uint8,
+                                count=len(rows))
+                nulls = torch.from_numpy(m).cuda()
+        for t, dt, what in ((bytes, torch.uint8, "bytes"),
+                            (offs, torch.int64, "offs")):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or \
+                    t.dim() != 1 or not t.is_contiguous():
+                raise OtbxError(3, f"text: {what} is a contiguous 1-D {dt} "
+                                   "tensor")
+        if len(offs) < 1:
+            raise OtbxError(3, "text: offs holds n + 1 entries")
+        if nulls is not None and (not isinstance(nulls, torch.Tensor) or
+                                  nulls.dtype != torch.uint8 or
+                                  nulls.dim() != 1 or
+                                  len(nulls) != len(offs) - 1 or
+                                  not nulls.is_contiguous()):
+            raise OtbxError(3, "text: a null mask is a uint8 tensor of the "
+                               "column's length")
+        self.bytes, self.offs, self.nulls = bytes, offs, nulls
+
+    def __len__(self):
+        return len(self.offs) - 1
+
+    def col(self):
+        """The otbx_textcol of this column."""
+        c = TextColDev()
+        c.bytes = self.bytes.data_ptr() if len(self.bytes) else None
+        c.offs = self.offs.data_ptr()
+        c.nulls = self.nulls.data_ptr() \
+            if self.nulls is not None and len(self) else None
+        c.nbytes = len(self.bytes)
+        return c
+
+    def slice(self, a, b):
+        """Rows [a, b) as a view: no byte is copied."""
+        n = len(self)
+        if not (isinstance(a, int) and isinstance(b, int) and 0 <= a <= b <= n):
+            raise OtbxError(3, "text: slice outside the column")
+        return GpuText(bytes=self.bytes, offs=self.offs[a:b + 1],
+                       nulls=None if self.nulls is None else self.nulls[a:b])
+
+    def to_list(self):
+        """The rows on the host: bytes, None under a NULL. Offsets are
+        clamped exactly as the kernels clamp them."""
+        raw = self.bytes.cpu().numpy().tobytes()
+        o = self.offs.cpu().tolist()
+        m = None if self.nulls is None else self.nulls.cpu().tolist()
+        nb = len(raw)
+        out = []
+        for i in range(len(o) - 1):
+            if m is not None and m[i]:
+                out.append(None)
+                continue
+            s = min(max(o[i], 0), nb)
+            e = min(max(o[i + 1], 0), nb)
+            out.append(raw[s:e] if e > s else b"")
+        return out
+
+    def gather(self, perm):
+        """Row perm[j] of this column as row j of a new GpuText (a selection
+        from GpuFilter, a permutation from GpuSort, row ids of a join:
+        entries may repeat and are clamped into the column). One host
+        synchronisation: the total byte count, to size the new bytes."""
+        if not isinstance(perm, torch.Tensor) or perm.dtype != torch.int64 \
+                or perm.dim() != 1 or not perm.is_contiguous():
+            raise OtbxError(3, "text: perm is a contiguous int64 tensor of "
+                               "row ids")
+        n, n_src = len(perm), len(self)
+        if n > 0 and n_src == 0:
+            raise OtbxError(3, "text: gather from an empty column")
+        L = lib()
+        wsb = C.c_size_t(0)
+        check(L.otbx_text_gather_workspace_bytes(C.c_int64(n), C.byref(wsb)),
+              "otbx_text_gather_workspace_bytes")
+        ws = torch.empty(max(wsb.value, 8) // 8, dtype=torch.int64,
+                         device="cuda")
+        doffs = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+        c = self.col()
+        pp = C.c_void_p(perm.data_ptr()) if n > 0 else None
+        call("otbx_text_gather_offsets", C.byref(c), C.c_int64(n_src), pp,
+             C.c_int64(n), C.c_void_p(ws.data_ptr()), C.c_size_t(wsb.value),
+             C.c_void_p(doffs.data_ptr()), _stream())
+        total = int(doffs[n].cpu().item())
+        dbytes = torch.empty(total, dtype=torch.uint8, device="cuda")
+        call("otbx_text_gather_bytes", C.byref(c), C.c_int64(n_src), pp,
+             C.c_int64(n), C.c_void_p(doffs.data_ptr()),
+             C.c_void_p(dbytes.data_ptr()) if total > 0 else None,
+             C.c_int64(total), _stream())
+        nulls = None
+        if self.nulls is not None:
+            # otbx_gather_u8 does not clamp its row ids
+            nulls = gather(self.nulls, torch.clamp(perm, 0, n_src - 1)) \
+                if n > 0 else torch.empty(0, dtype=torch.uint8, device="cuda")
+        return GpuText(bytes=dbytes, offs=doffs, nulls=nulls)
+
+
+class GpuTextPred(CustomScanState):
+    """One predicate over a text column (textlike / textnlike, like.c:269;
+    texteq … text_ge under C collation, varlena.c:1874): `text` OP `rhs`
+    with op "like", "not like", "=", "<>", "<", "<=", ">" or ">="; rhs a
+    constant (bytes / str, at most 256 bytes; a LIKE pattern in the backslash
+    convention — see like_escape) or, for the comparisons, a second GpuText
+    of the same length. With `sel`, the int64 selection GpuFilter yielded,
+    only the selected rows are evaluated, read through it. encoding "utf8"
+    or "sb" decides how `_` and the restart after `%` advance. Yields ONE
+    tuple (bool_u8, nulls_or_None); term() is that as a GpuFilter term.
+    Contract in include/otbx.h (otbx_text_pred)."""
+
+    def __init__(self, text, op, rhs, sel=None, encoding="utf8"):
+        super().__init__()
+        if not isinstance(text, GpuText):
+            raise OtbxError(3, "text predicate: the left operand is a GpuText")
+        if op not in TXT_OPS:
+            raise OtbxError(3, f"text predicate: unknown operator {op!r}")
+        if encoding not in TEXT_ENCODINGS:
+            raise OtbxError(3, f"text predicate: unknown encoding {encoding!r}")
+        if isinstance(rhs, GpuText):
+            if op in ("like", "not like"):
+                raise OtbxError(3, "text predicate: a LIKE pattern is a "
+                                   "constant")
+            if len(rhs) != len(text):
+                raise OtbxError(3, "text predicate: columns differ in length")
+        else:
+            rhs = _text_bytes(rhs, "the right operand")
+            if len(rhs) > MAX_TEXT_CONST:
+                raise OtbxError(3, "text predicate: a constant has at most "
+                                   f"{MAX_TEXT_CONST} bytes")
+            if op in ("like", "not like"):
+                # a backslash that escapes nothing (odd run at the end)
+                k = len(rhs) - len(rhs.rstrip(b"\\"))
+                if k % 2 == 1:
+                    raise OtbxError(3, "LIKE pattern must not end with "
+                                       "escape character")
+        if sel is not None and (not isinstance(sel, torch.Tensor) or
+                                sel.dtype != torch.int64 or sel.dim() != 1 or
+                                not sel.is_contiguous()):
+            raise OtbxError(3, "text predicate: sel is an int64 tensor of "
+                               "row ids")
+        self.text, self.op, self.rhs = text, op, rhs
+        self.sel, self.encoding = sel, encoding
+        self.n_src = len(text)
+        self.n = len(sel) if sel is not None else self.n_src
+        if self.n > 0 and self.n_src == 0:
+            raise OtbxError(3, "text predicate: sel over an empty column")
+        self.nullable = text.nulls is not None or \
+            (isinstance(rhs, GpuText) and rhs.nulls is not None)
+        self.value = None
+        self.nulls = None
+        self.pred_ms = None
+
+    def pred(self):
+        """The otbx_textpred handed to otbx_text_pred (and the right column
+        it points to, which must outlive the call)."""
+        p = TextPredDev()
+        p.left = self.text.col()
+        p.op = TXT_OPS[self.op]
+        p.encoding = TEXT_ENCODINGS[self.encoding]
+        right = None
+        if isinstance(self.rhs, GpuText):
+            right = self.rhs.col()
+            p.right = C.pointer(right)
+        else:
+            p.clen = len(self.rhs)
+            C.memmove(p.cbytes, self.rhs, len(self.rhs))
+        return p, right
+
+    def _run(self):
+        n = self.n
+        # an empty tensor has no address: one spare byte behind each output
+        obuf = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda")
+        nbuf = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda") \
+            if self.nullable else None
+        p, _right = self.pred()   # _right: what p.right points to
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        call("otbx_text_pred", C.byref(p),
+             C.c_void_p(self.sel.data_ptr())
+             if self.sel is not None and n > 0 else None,
+             C.c_int64(n), C.c_int64(self.n_src), C.c_void_p(obuf.data_ptr()),
+             C.c_void_p(nbuf.data_ptr()) if nbuf is not None else None,
+             _stream())
+        ev1.record()
+        # no synchronisation here: explain() reads the events when asked
+        self._ev = (ev0, ev1)
+        self.pred_ms = None
+        self.value = obuf[:n]
+        self.nulls = nbuf[:n] if nbuf is not None else None
+        return [(self.value, self.nulls)]
+
+    def term(self):
+        """The predicate as a term of GpuFilter's qual: TRUE rows pass, FALSE
+        and NULL rows do not (runs the node if it has not run)."""
+        if self.value is None:
+            self._run()
+        return qual_term(self.value, "=", 1, nulls=self.nulls)
+
+    def explain(self):
+        if self.value is None:
+            return None
+        if self.pred_ms is None:
+            self._ev[1].synchronize()
+            self.pred_ms = self._ev[0].elapsed_time(self._ev[1])
+        return {"text_pred": self.pred_ms}
 
 
 class GpuHashAgg(CustomScanState):

@@ -31,6 +31,13 @@ distinct from the fused query pipelines.
                                    its sort, next to otbx_window, the hash
                                    aggregate and a plain-torch composition
                                    (writes profiles/groupagg_ops.txt, or PATH)
+  generic_ops_bench.py --text [--rows N[,N..]] [--out PATH]
+                                   otbx_text_pred (LIKE / compare, staged and
+                                   forced-direct) and the text gather on
+                                   part-name-, comment- and shipmode-shaped
+                                   columns at 20 M and 200 M rows, next to
+                                   numpy's np.char.find on one core (writes
+                                   profiles/text_ops.txt, or PATH)
 """
 import ctypes as C
 import os
@@ -1012,8 +1019,263 @@ def bench_project(out_path):
         f.write("\n".join(lines) + "\n")
 
 
+# ---------------- text: LIKE / compare predicates and the gather ----------
+
+P_NAME_WORDS = (
+    "almond antique aquamarine azure beige bisque black blanched blue blush "
+    "brown burlywood burnished chartreuse chiffon chocolate coral cornflower "
+    "cornsilk cream cyan dark deep dim dodger drab firebrick floral forest "
+    "frosted gainsboro ghost goldenrod green grey honeydew hot indian ivory "
+    "khaki lace lavender lawn lemon light lime linen magenta maroon medium "
+    "metallic midnight mint misty moccasin navajo navy olive orange orchid "
+    "pale papaya peach peru pink plum powder puff purple red rose rosy royal "
+    "saddle salmon sandy seashell sienna sky slate smoke snow spring steel "
+    "tan thistle tomato turquoise violet wheat white yellow").split()
+COMMENT_WORDS = (
+    "special requests packages accounts deposits pending furiously carefully "
+    "quickly slyly blithely ironic final regular express bold even silent "
+    "unusual theodolites pinto beans foxes instructions dependencies excuses "
+    "platelets asymptotes courts dolphins sleep wake nag haggle about above "
+    "according across after against along the").split()
+SHIP_MODES = ["REG AIR", "AIR", "RAIL", "SHIP", "TRUCK", "MAIL", "FOB"]
+
+
+def _word_rows(words, per_row, n, gen):
+    """n rows of per_row random words joined by single spaces, built on the
+    device by the text gather itself: a dictionary column holds every word
+    with and without a trailing space, one gathered entry per word, and the
+    row offsets are every per_row-th offset of the gathered column. A 1 %
+    null mask rides along (the NULL rows keep their bytes)."""
+    d = ex.GpuText([w + " " for w in words] + list(words))
+    ids = torch.randint(0, len(words), (n, per_row), device="cuda",
+                        generator=gen)
+    ids[:, per_row - 1] += len(words)            # last word: no space
+    g = d.gather(ids.reshape(-1))
+    del ids
+    offs = g.offs[::per_row].contiguous()
+    nulls = (torch.rand(n, device="cuda", generator=gen) < 0.01) \
+        .to(torch.uint8)
+    return ex.GpuText(bytes=g.bytes, offs=offs, nulls=nulls)
+
+
+class _TextPredCall:
+    """otbx_text_pred with the outputs preallocated."""
+
+    def __init__(self, text, op, rhs, sel=None):
+        self.node = ex.GpuTextPred(text, op, rhs, sel=sel)
+        self.p, self.right = self.node.pred()
+        self.n, self.n_src, self.sel = self.node.n, self.node.n_src, sel
+        self.out = torch.empty(self.n, dtype=torch.uint8, device="cuda")
+        self.nulls = torch.empty(self.n, dtype=torch.uint8, device="cuda")
+        self.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def __call__(self):
+        call("otbx_text_pred", C.byref(self.p),
+             C.c_void_p(self.sel.data_ptr()) if self.sel is not None else None,
+             C.c_int64(self.n), C.c_int64(self.n_src),
+             C.c_void_p(self.out.data_ptr()),
+             C.c_void_p(self.nulls.data_ptr()), self.stream)
+
+    def count(self):
+        return int(((self.out != 0) & (self.nulls == 0)).sum().item())
+
+
+def _torch_text_gather(text, perm):
+    """the gathered bytes and offsets built with plain torch"""
+    starts, ends = text.offs[:-1][perm], text.offs[1:][perm]
+    lens = ends - starts
+    doffs = torch.zeros(len(perm) + 1, dtype=torch.int64, device="cuda")
+    torch.cumsum(lens, 0, out=doffs[1:])
+    total = int(doffs[-1].item())
+    src = torch.repeat_interleave(starts - doffs[:-1], lens) + \
+        torch.arange(total, device="cuda")
+    return text.bytes[src], doffs
+
+
+def bench_text(out_path, sizes):
+    import numpy as np
+    sys.path.insert(0, os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from text_ref import like_rec
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    say("# tools/generic_ops_bench.py --text — best / worst of 5 wall time "
+        "after torch.cuda.synchronize(), columns staged, outputs "
+        "preallocated; every column carries a 1 % null mask")
+    say("# predicate: algorithmic B per row = text bytes + 8 offsets + 1 mask "
+        "+ 2 out (value, null) [+ 8 selection entry, per output row]")
+    say("# gather: algorithmic B per output row = 2 x text bytes + 16 offsets "
+        "(read, write) + 8 perm; offsets pass and byte pass timed together, "
+        "with the one read-back of the total between them")
+    say("# staged = OTBX_TEXT_STAGE=1, tile bytes copied to LDS first; direct "
+        "= OTBX_TEXT_STAGE=0, every row read from global memory; default = "
+        "unset, the library's rule (staged only for a LIKE with a % before "
+        "the pattern's last token)")
+    gen = torch.Generator(device="cuda").manual_seed(23)
+
+    def pred_line(tag, what, text, op, rhs, sel=None):
+        res = {}
+        for mode in ("staged", "direct", "default"):
+            if mode == "default":
+                os.environ.pop("OTBX_TEXT_STAGE", None)
+            else:
+                os.environ["OTBX_TEXT_STAGE"] = "1" if mode == "staged" \
+                    else "0"
+            pc = _TextPredCall(text, op, rhs, sel=sel)
+            b, w = _best_of_5(pc)
+            res[mode] = (b, w, pc.count(), pc.out.clone())
+            rows = pc.n
+            if sel is None:
+                tbytes = int((text.offs[-1] - text.offs[0]).item())
+                alg = tbytes + rows * 11
+            else:
+                tbytes = int((text.offs[1:][sel] - text.offs[:-1][sel])
+                             .sum().item())
+                alg = tbytes + rows * 19
+            tbs = alg / b / 1e12
+            say(f"({tag}) rows={rows:_} {what} [{mode}]: best {b*1e3:8.3f} ms"
+                f"  worst {w*1e3:8.3f} ms (spread {(w-b)/b*100:.1f} %)  "
+                f"{alg/max(rows,1):.1f} B/row algorithmic = {alg/1e9:.2f} GB  "
+                f"{tbs:5.2f} TB/s = {tbs*1e12/COPY_CEILING*100:4.1f} % of the "
+                f"6.29 TB/s copy ceiling; TRUE rows {res[mode][2]:_}")
+            del pc
+        os.environ.pop("OTBX_TEXT_STAGE", None)
+        same = bool(torch.equal(res["staged"][3], res["direct"][3])) and \
+            bool(torch.equal(res["default"][3], res["direct"][3]))
+        say("    staged / direct time ratio "
+            f"{res['staged'][0]/res['direct'][0]:.2f}; same result in all "
+            f"three: {same}")
+        assert same, f"case ({tag}): staged and direct disagree"
+        return res["staged"][3]
+
+    def gather_line(tag, what, text, perm, verify):
+        def run():
+            return text.gather(perm)
+        b, w = _best_of_5(run)
+        g = run()
+        rows, tbytes = len(perm), len(g.bytes)
+        alg = 2 * tbytes + rows * 24
+        tbs = alg / b / 1e12
+        say(f"({tag}) rows={rows:_} {what}: best {b*1e3:8.3f} ms  worst "
+            f"{w*1e3:8.3f} ms (spread {(w-b)/b*100:.1f} %)  "
+            f"{alg/max(rows,1):.1f} B/row algorithmic = {alg/1e9:.2f} GB  "
+            f"{tbs:5.2f} TB/s = {tbs*1e12/COPY_CEILING*100:4.1f} % of the "
+            "6.29 TB/s copy ceiling")
+        if verify:
+            tb, toffs = _torch_text_gather(text, perm)
+            same = bool(torch.equal(tb, g.bytes)) and \
+                bool(torch.equal(toffs, g.offs))
+            say(f"    byte-equal to the torch-built copy: {same}")
+            assert same, f"case ({tag}): gather differs from torch"
+            del tb, toffs
+        else:
+            say("    byte comparison with torch: not run at this size")
+        del g
+        torch.cuda.empty_cache()
+
+    for n in sizes:
+        say()
+        say(f"## {n:_} rows")
+        name = _word_rows(P_NAME_WORDS, 5, n, gen)
+        nb = len(name.bytes)
+        say(f"# part names: {nb/n:.1f} B/row, {nb/1e9:.2f} GB")
+        green = pred_line("a", "p_name LIKE '%green%' (Q9)", name, "like",
+                          "%green%")
+        pred_line("b", "p_name LIKE 'forest%' (Q20)", name, "like", "forest%")
+
+        if n == sizes[0]:
+            # counted: the first 1 M rows against the reference's matcher
+            # (the prefix is copied out first, so that only it goes to the
+            # host)
+            m = min(n, 1_000_000)
+            host = name.slice(0, m).gather(
+                torch.arange(m, device="cuda")).to_list()
+            want = sum(1 for r in host if r is not None and
+                       like_rec(r, b"%green%"))
+            pm = _TextPredCall(name.slice(0, m), "like", "%green%")
+            pm()
+            say(f"    '%green%' on the first {m:_} rows: otbx_text_pred "
+                f"selects {pm.count():_}, the reference loop {want:_}")
+            assert pm.count() == want
+            del pm, host
+
+            # numpy on one core over the same bytes, as a fixed-width array
+            width = int((name.offs[1:] - name.offs[:-1]).max().item())
+            idx = name.offs[:-1, None] + torch.arange(width, device="cuda")
+            keep = idx < name.offs[1:, None]
+            fixed = torch.where(keep, name.bytes[idx.clamp_(max=nb - 1)],
+                                torch.zeros((), dtype=torch.uint8,
+                                            device="cuda"))
+            arr = fixed.cpu().numpy().view(f"S{width}").reshape(-1)
+            del idx, keep, fixed
+            t0 = time.time()
+            hit = np.char.find(arr, b"green") >= 0
+            th = time.time() - t0
+            valid = name.nulls.cpu().numpy() == 0
+            same = bool(np.array_equal(hit & valid, green.cpu().numpy() != 0))
+            say(f"    numpy np.char.find(names, 'green') >= 0 on one core, "
+                f"S{width} array: {th*1e3:.0f} ms (one run); same rows: {same}")
+            assert same
+            del arr, hit
+
+        key = torch.randint(0, 100, (n,), dtype=torch.int32, device="cuda",
+                            generator=gen)
+        fc = _FilterCall([[ex.qual_term(key, "<", 6)]])
+        fc()
+        sel = fc.sel[:fc.count()].clone()
+        del fc
+        pred_line("e", f"p_name LIKE '%green%' through a "
+                  f"{len(sel)/n*100:.1f} % selection", name, "like",
+                  "%green%", sel=sel)
+        srt = ex.GpuSort([torch.randint(0, 2**62, (n,), device="cuda",
+                                        generator=gen)])
+        srt.BeginCustomScan()
+        perm = srt.ExecCustomScan()
+        srt.EndCustomScan()
+        del srt
+        torch.cuda.empty_cache()
+        gather_line("f", "p_name gathered through a sort permutation", name,
+                    perm, verify=n <= 20_000_000)
+        del perm
+        gather_line("g", f"p_name gathered through the "
+                    f"{len(sel)/n*100:.1f} % selection", name, sel,
+                    verify=True)
+        del name, sel, key, green
+        torch.cuda.empty_cache()
+
+        comment = _word_rows(COMMENT_WORDS, 8, n, gen)
+        say(f"# comments: {len(comment.bytes)/n:.1f} B/row")
+        pred_line("c", "o_comment LIKE '%special%requests%' (Q13)", comment,
+                  "like", "%special%requests%")
+        del comment
+        torch.cuda.empty_cache()
+        mode = _word_rows(SHIP_MODES, 1, n, gen)
+        say(f"# ship modes: {len(mode.bytes)/n:.1f} B/row")
+        pred_line("d", "l_shipmode = 'MAIL' (Q12)", mode, "=", "MAIL")
+        del mode
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
     ex.init_device(0)
+    if "--text" in sys.argv:
+        repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        out_path = os.path.join(repo, "profiles", "text_ops.txt")
+        if "--out" in sys.argv:
+            out_path = sys.argv[sys.argv.index("--out") + 1]
+        sizes = [20_000_000, 200_000_000]
+        if "--rows" in sys.argv:
+            sizes = [int(x) for x in
+                     sys.argv[sys.argv.index("--rows") + 1].split(",")]
+        bench_text(out_path, sizes)
+        sys.exit(0)
     if "--project" in sys.argv:
         repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         out_path = os.path.join(repo, "profiles", "project_ops.txt")
