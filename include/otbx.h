@@ -55,6 +55,11 @@
  *                            logic, CASE and COALESCE (execExprInterp.c)
  *                            over selected rows, with the reference's
  *                            first-error behaviour in a device error slot
+ *   otbx_text_rank         — text as a sort, group or join key: bttextcmp
+ *                            (utils/adt/varlena.c:1998) as the sort support
+ *                            of a text ORDER BY, and texteq + hashing for a
+ *                            text GROUP BY / join, both replaced by ordered
+ *                            dictionary codes the int64 operators take
  *   merge (Coordinator)   — NOT here: the shard merge (execFragment.c:3877)
  *                            is a collective over ranks, done by the host
  *                            layer with RCCL (torch.distributed) on the
@@ -1194,6 +1199,71 @@ otbx_status otbx_text_gather_bytes(const otbx_textcol *src, int64_t n_src,
                                    const int64_t *dst_offs_dev,
                                    uint8_t *dst_bytes_dev, int64_t dst_nbytes,
                                    void *stream);
+
+/* ---- GPU text keys: ordered dictionary codes for sort, group, join ----
+ * otbx_text_rank gives every row of a text column the dense rank of its
+ * string under C collation: an order-preserving dictionary encoding. The
+ * codes are an ordinary int64 key column and the column's null mask is the
+ * mask the other operators take, so ORDER BY, PARTITION BY, GROUP BY,
+ * DISTINCT, MIN / MAX and equi-joins over text run through otbx_sort_perm,
+ * otbx_window, otbx_group_agg, otbx_agg_i64* and otbx_join_i64* unchanged;
+ * the pinned otbx_sortkey / otbx_qualterm / otbx_aggcall get no text type.
+ *
+ * ROWS. The 1..OTBX_MAX_TEXT_RANK_COLS columns of the set form one virtual
+ * column of n_total = Σ n[c] rows, numbered consecutively, column 0 first.
+ * Ranking several columns jointly is what a text join needs: both sides get
+ * codes from one dictionary, and no byte is copied.
+ *
+ * CODES. codes_dev[i] is the number of distinct non-NULL strings of the
+ * whole set that are strictly smaller than row i, under varstr_cmp with
+ * lc_collate_is_c (utils/adt/varlena.c:1614-1629): memcmp over the common
+ * prefix, bytes UNSIGNED, then the shorter string is smaller. So
+ * code(a) < code(b) ⇔ a < b, and code(a) == code(b) ⇔ same length and same
+ * bytes. A 0x00 byte is an ordinary byte: "a" < "a\0" < "a\0\0" < "a\1". The
+ * empty string is the smallest value and is not NULL. A NULL row gets code
+ * -1; its bytes are never read.
+ *
+ * OUTPUTS. *ndistinct_dev = D. dict_row_dev[c], c < D, is the smallest
+ * virtual row holding code c (the first occurrence: unique); it feeds
+ * otbx_text_gather_* to materialise the dictionary in sorted order. Entries
+ * at and past D are not written. *rounds_host is the number of refinement
+ * rounds run: round r sorts the rows still undecided by bytes [8r, 8r+8)
+ * with otbx_sort_perm, so rounds <= 1 + Lmax / 8 (Lmax the longest non-NULL
+ * row), and rounds == 1 whenever no two non-NULL rows that share their
+ * first 8 bytes are both longer than 8 bytes.
+ *
+ * Offsets are clamped as otbx_text_pred clamps them; broken offsets can give
+ * wrong codes but never an access outside bytes. Results are bit-identical
+ * from run to run.
+ *
+ * SYNCHRONOUS, unlike otbx_sort_perm and otbx_filter_sel: the call reads
+ * back one int64 per round (the rows still undecided) and returns with the
+ * stream drained, like otbx_build_q1codes. A dictionary is built once per
+ * column, at staging or plan time.
+ *
+ * Checked before any HIP call, each returning OTBX_ERR_INVALID: ts or
+ * ndistinct_dev NULL; ncols outside 1..4; an n[c] < 0; n_total > INT32_MAX;
+ * per column bytes NULL with nbytes > 0, offs NULL with n[c] > 0,
+ * nbytes < 0; codes_dev NULL with n_total > 0; ws_bytes below
+ * otbx_text_rank_workspace_bytes(n_total); ws_dev NULL or not 16-byte
+ * aligned. n_total == 0 is valid: *ndistinct_dev = 0, rounds 0.
+ * otbx_text_rank_workspace_bytes is pure host code, monotone in n_total. */
+#define OTBX_MAX_TEXT_RANK_COLS 4
+typedef struct {
+    int32_t      ncols;                         /* 1..OTBX_MAX_TEXT_RANK_COLS */
+    int32_t      _pad;
+    otbx_textcol col[OTBX_MAX_TEXT_RANK_COLS];
+    int64_t      n[OTBX_MAX_TEXT_RANK_COLS];    /* rows of each column */
+} otbx_textset;
+
+otbx_status otbx_text_rank_workspace_bytes(int64_t n_total, size_t *bytes);
+otbx_status otbx_text_rank(const otbx_textset *ts,
+                           void *ws_dev, size_t ws_bytes,
+                           int64_t *codes_dev,      /* n_total entries            */
+                           int64_t *dict_row_dev,   /* cap n_total; may be NULL   */
+                           int64_t *ndistinct_dev,  /* int64[1], required         */
+                           int32_t *rounds_host,    /* may be NULL                */
+                           void *stream);
 
 /* ---- repartition exchange ----
  * The GPU half of the reference's "Distribute results by H: col" exchange

@@ -179,6 +179,19 @@ class TextPredDev(C.Structure):
 
 assert C.sizeof(TextColDev) == 32 and C.sizeof(TextPredDev) == 312
 
+MAX_TEXT_RANK_COLS = 4                       # OTBX_MAX_TEXT_RANK_COLS
+
+
+class TextSetDev(C.Structure):
+    """otbx_textset: the 1..4 text columns otbx_text_rank ranks jointly,
+    168 bytes."""
+    _fields_ = [("ncols", C.c_int32), ("_pad", C.c_int32),
+                ("col", TextColDev * MAX_TEXT_RANK_COLS),
+                ("n", C.c_int64 * MAX_TEXT_RANK_COLS)]
+
+
+assert C.sizeof(TextSetDev) == 168
+
 
 class PartDev(C.Structure):
     _fields_ = [
@@ -219,6 +232,7 @@ def lib():
         _lib.otbx_filter_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_group_agg_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_text_gather_workspace_bytes.argtypes = [i64, szp]
+        _lib.otbx_text_rank_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_q1code_plan.argtypes = [
             C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
             C.POINTER(Q1CodeDesc), C.POINTER(C.c_int32)]
@@ -263,4 +277,5 @@ EXPORTED_SYMBOLS = [
     "otbx_group_agg_workspace_bytes", "otbx_group_agg",
     "otbx_text_pred", "otbx_text_gather_workspace_bytes",
     "otbx_text_gather_offsets", "otbx_text_gather_bytes",
+    "otbx_text_rank_workspace_bytes", "otbx_text_rank",
 ]

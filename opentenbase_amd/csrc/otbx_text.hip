@@ -46,6 +46,7 @@
 #include <string.h>
 
 #include "otbx_common.h"
+#include "otbx_textcol.h"   /* txt_clamp, txt_row, txt_col_ok */
 
 #define TXT_THREADS 256
 #define TXT_TILE TXT_THREADS          /* rows per workgroup */
@@ -82,11 +83,6 @@ struct txt_args {
     uint8_t byte[OTBX_MAX_TEXT_CONST];   /* LIT: the byte; constant bytes */
     uint8_t kind[OTBX_MAX_TEXT_CONST];   /* TOK_* (LIKE only) */
 };
-
-__device__ __forceinline__ int64_t txt_clamp(int64_t v, int64_t hi)
-{
-    return v < 0 ? 0 : (v > hi ? hi : v);
-}
 
 /* NextChar (like.c:142): one byte, then every continuation byte; one byte
  * in a single-byte encoding. Never past len. */
@@ -159,20 +155,6 @@ __device__ __forceinline__ bool txt_cmp_op(int op, int c)
     case OTBX_TXT_GT: return c > 0;
     default:          return c >= 0;
     }
-}
-
-/* row r of a column as (clamped start, length): offsets outside [0, nbytes]
- * are clamped into it and a negative length reads as 0 */
-__device__ __forceinline__ void txt_row(const otbx_textcol &c, int64_t r,
-                                        int64_t *s, int *len)
-{
-    const int64_t a = txt_clamp(c.offs[r], c.nbytes);
-    const int64_t b = txt_clamp(c.offs[r + 1], c.nbytes);
-    *s = a;
-    /* a row longer than INT32_MAX cannot exist: nbytes of one column fits
-     * the device, the cursors are ints — cut it there */
-    const int64_t l = b > a ? b - a : 0;
-    *len = l > (int64_t)INT32_MAX ? INT32_MAX : (int)l;
 }
 
 template <int KIND, typename P>
@@ -497,17 +479,6 @@ static bool txt_prepare_like(const uint8_t *pat, int plen, txt_args *a)
         a->byte[np++] = pat[i++];
     }
     a->np = np;
-    return true;
-}
-
-static bool txt_col_ok(const otbx_textcol *c, int64_t n_src)
-{
-    if (c->nbytes < 0)
-        return false;
-    if (c->nbytes > 0 && !c->bytes)
-        return false;
-    if (n_src > 0 && !c->offs)
-        return false;
     return true;
 }
 

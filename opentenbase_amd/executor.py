@@ -16,11 +16,11 @@ import math
 
 import torch
 
-from ._lib import (AGG_FUNCS, MAX_AGGS, MAX_TEXT_CONST, TEXT_ENCODINGS,
-                   TXT_OPS, AggCallsDev, CustomerDev, ExprDev, KeysetDev,
-                   LineitemDev, OrdersDev, OtbxError, PartDev, Q1_DICT_MAX,
-                   Q1CodeDesc, QualDev, SortSpecDev, TextColDev, TextPredDev,
-                   WindowOutDev, call, check, lib)
+from ._lib import (AGG_FUNCS, MAX_AGGS, MAX_TEXT_CONST, MAX_TEXT_RANK_COLS,
+                   TEXT_ENCODINGS, TXT_OPS, AggCallsDev, CustomerDev, ExprDev,
+                   KeysetDev, LineitemDev, OrdersDev, OtbxError, PartDev,
+                   Q1_DICT_MAX, Q1CodeDesc, QualDev, SortSpecDev, TextColDev,
+                   TextPredDev, TextSetDev, WindowOutDev, call, check, lib)
 
 Q1_SLOT_ORDER = [(b"A", b"F"), (b"A", b"O"), (b"N", b"F"),
                  (b"N", b"O"), (b"R", b"F"), (b"R", b"O")]
@@ -1762,6 +1762,183 @@ class GpuText:
             nulls = gather(self.nulls, torch.clamp(perm, 0, n_src - 1)) \
                 if n > 0 else torch.empty(0, dtype=torch.uint8, device="cuda")
         return GpuText(bytes=dbytes, offs=doffs, nulls=nulls)
+
+    def rank(self, *others):
+        """Ordered dictionary codes of this column, ranked jointly with
+        `others` (up to four columns in all): runs a GpuTextRank node and
+        returns its TextRank."""
+        node = GpuTextRank([self, *others])
+        node.BeginCustomScan()
+        try:
+            return node.ExecCustomScan()
+        finally:
+            node.EndCustomScan()
+
+
+class TextRank:
+    """What GpuTextRank yields. `codes`: one int64 tensor per input column,
+    views of one buffer — the dense rank of every row's string among the
+    distinct non-NULL strings of all the columns, -1 under a NULL.
+    `ndistinct`: D. `dict_rows`: int64[D], the first virtual row (the
+    columns numbered through, column 0 first) holding each code. `rounds`:
+    refinement rounds the kernels ran."""
+
+    def __init__(self, columns, codes, ndistinct, dict_rows, rounds):
+        self.columns = columns
+        self.codes = codes
+        self.ndistinct = ndistinct
+        self.dict_rows = dict_rows
+        self.rounds = rounds
+        self._dict = None
+
+    def dictionary(self):
+        """The distinct strings in order, as a GpuText of D rows without a
+        mask: row c is the string of code c. The inputs' bytes are not
+        copied: each column gathers its own first occurrences, and the
+        dictionary-sized pieces are put in order by one more gather."""
+        if self._dict is not None:
+            return self._dict
+        d = self.ndistinct
+        if d == 0:
+            self._dict = GpuText(
+                bytes=torch.empty(0, dtype=torch.uint8, device="cuda"),
+                offs=torch.zeros(1, dtype=torch.int64, device="cuda"))
+            return self._dict
+        parts, where = [], []
+        start = 0
+        for col in self.columns:
+            end = start + len(col)
+            pos = torch.nonzero((self.dict_rows >= start) &
+                                (self.dict_rows < end)).reshape(-1)
+            if len(pos):
+                g = col.gather((self.dict_rows[pos] - start).contiguous())
+                parts.append(g)
+                where.append(pos)
+            start = end
+        if len(parts) == 1:
+            out = parts[0]
+        else:
+            base, offs = 0, []
+            for g in parts:
+                offs.append(g.offs[:-1] + base)
+                base += int(len(g.bytes))
+            offs.append(torch.tensor([base], dtype=torch.int64, device="cuda"))
+            cat = GpuText(bytes=torch.cat([g.bytes for g in parts]),
+                          offs=torch.cat(offs))
+            inv = torch.empty(d, dtype=torch.int64, device="cuda")
+            inv[torch.cat(where)] = torch.arange(d, dtype=torch.int64,
+                                                 device="cuda")
+            out = cat.gather(inv)
+        self._dict = GpuText(bytes=out.bytes, offs=out.offs)
+        return self._dict
+
+    def decode(self, codes):
+        """codes (int64 tensor) → GpuText: the dictionary's row per code,
+        NULL for a code of -1 (what a NULL row got, and what MIN / MAX over
+        no row leaves)."""
+        if not isinstance(codes, torch.Tensor) or codes.dtype != torch.int64 \
+                or codes.dim() != 1:
+            raise OtbxError(3, "text rank: codes is an int64 tensor")
+        codes = codes.contiguous()
+        nulls = (codes < 0).to(torch.uint8)
+        if self.ndistinct == 0:
+            return GpuText(
+                bytes=torch.empty(0, dtype=torch.uint8, device="cuda"),
+                offs=torch.zeros(len(codes) + 1, dtype=torch.int64,
+                                 device="cuda"),
+                nulls=torch.ones(len(codes), dtype=torch.uint8,
+                                 device="cuda"))
+        g = self.dictionary().gather(codes)   # -1 is clamped to row 0
+        return GpuText(bytes=g.bytes, offs=g.offs, nulls=nulls)
+
+
+class GpuTextRank(CustomScanState):
+    """Text as a sort, group or join key (otbx_text_rank): an
+    order-preserving dictionary encoding of one to four GpuText columns,
+    ranked jointly so that equal strings of different columns get one code.
+    code(a) < code(b) ⇔ a < b under C collation (varstr_cmp with
+    lc_collate_is_c, varlena.c:1614-1629; bttextcmp varlena.c:1998),
+    code(a) == code(b) ⇔ texteq; NULL rows get -1 and keep their mask.
+    Yields ONE tuple, a TextRank. The call is synchronous (one int64 read
+    back per refinement round); build a dictionary once per column.
+
+    The codes are an ordinary int64 key column, the column's mask is the
+    mask the other nodes take, and those nodes do not change:
+      ORDER BY t DESC NULLS FIRST, x
+          GpuSort([r.codes[0], x], descending=[True, False],
+                  nulls_first=[True, None], nulls=[t.nulls, None])
+      GROUP BY t
+          GpuGroupAgg([r.codes[0]], aggs, key_nulls=[t.nulls]) or
+          GpuHashAgg(r.codes[0], vals, key_null=t.nulls), then
+          r.decode(group keys)
+      MIN(t) / MAX(t)  (text_smaller / text_larger, varlena.c:2819-2840)
+          MIN / MAX over the codes with t.nulls as the value mask, then
+          r.decode(result)
+      a.t = b.t
+          r = a.t.rank(b.t); GpuHashJoin(r.codes[0], r.codes[1],
+          build_null=a.t.nulls, probe_null=b.t.nulls)
+    Codes are local to this call (to one DataNode);
+    fragment.merge_text_dictionaries maps them to global ones."""
+
+    def __init__(self, columns):
+        super().__init__()
+        if isinstance(columns, GpuText):
+            columns = [columns]
+        self.columns = list(columns)
+        if not 1 <= len(self.columns) <= MAX_TEXT_RANK_COLS:
+            raise OtbxError(3, "text rank: 1..%d columns" % MAX_TEXT_RANK_COLS)
+        for c in self.columns:
+            if not isinstance(c, GpuText):
+                raise OtbxError(3, "text rank: every column is a GpuText")
+        self.n_total = sum(len(c) for c in self.columns)
+        if self.n_total > 2**31 - 1:
+            raise OtbxError(3, "text rank: more than 2^31 - 1 rows")
+        self.result = None
+        self.rank_ms = None
+
+    def textset(self):
+        """The otbx_textset handed to otbx_text_rank."""
+        ts = TextSetDev()
+        ts.ncols = len(self.columns)
+        for i, c in enumerate(self.columns):
+            ts.col[i] = c.col()
+            ts.n[i] = len(c)
+        return ts
+
+    def _run(self):
+        import time
+        L = lib()
+        n = self.n_total
+        wsb = C.c_size_t(0)
+        check(L.otbx_text_rank_workspace_bytes(C.c_int64(n), C.byref(wsb)),
+              "otbx_text_rank_workspace_bytes")
+        ws = torch.empty((wsb.value + 15) // 16 * 2, dtype=torch.int64,
+                         device="cuda")
+        # an empty tensor has no address: one spare entry behind each output
+        codes = torch.empty(max(n, 1), dtype=torch.int64, device="cuda")
+        drow = torch.empty(max(n, 1), dtype=torch.int64, device="cuda")
+        nd = torch.zeros(1, dtype=torch.int64, device="cuda")
+        rounds = C.c_int32(0)
+        ts = self.textset()
+        t0 = time.perf_counter()
+        call("otbx_text_rank", C.byref(ts), C.c_void_p(ws.data_ptr()),
+             C.c_size_t(wsb.value), C.c_void_p(codes.data_ptr()),
+             C.c_void_p(drow.data_ptr()), C.c_void_p(nd.data_ptr()),
+             C.byref(rounds), _stream())
+        # the call returns with the stream drained: a host clock is exact
+        self.rank_ms = (time.perf_counter() - t0) * 1e3
+        d = int(nd.cpu().item())
+        views, start = [], 0
+        for c in self.columns:
+            views.append(codes[start:start + len(c)])
+            start += len(c)
+        self.result = TextRank(self.columns, views, d, drow[:d], rounds.value)
+        return [self.result]
+
+    def explain(self):
+        if self.result is None:
+            return None
+        return {"text_rank": self.rank_ms, "rounds": self.result.rounds}
 
 
 class GpuTextPred(CustomScanState):

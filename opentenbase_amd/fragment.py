@@ -398,6 +398,42 @@ def merge_group_partials(keys, aggs, key_nulls=None, descending=None,
     return combine_group_partials(gk, gn, flags, ga)
 
 
+def merge_text_dictionaries(local_dictionary):
+    """Text codes (executor.GpuTextRank) are local to a DataNode: every rank
+    ranks its own strings. This all-gathers the ranks' dictionaries (row
+    lengths and bytes, through allgather_variable) and builds the global
+    sorted distinct list on the host — dictionary-sized numpy / Python, like
+    merge_group_partials. local_dictionary: the rank's distinct strings in
+    code order, a GpuText (TextRank.dictionary()) or a list of bytes.
+    Returns (global_dictionary, remap): the global list of bytes in C
+    collation order (Python's bytes order: memcmp, then the shorter first)
+    and an int64 numpy array with remap[local code] = global code. After
+    codes = remap[codes] the text-keyed partials go through
+    merge_group_partials / merge_sorted_partials unchanged. With one rank
+    or no process group it is the identity."""
+    import numpy as np
+    rows = local_dictionary.to_list() if hasattr(local_dictionary, "to_list") \
+        else [None if r is None else bytes(r) for r in local_dictionary]
+    if any(r is None for r in rows):
+        raise OtbxError(3, "text dictionary: a dictionary holds no NULL")
+    if not is_dist() or dist.get_world_size() == 1:
+        return rows, np.arange(len(rows), dtype=np.int64)
+    dev = "cuda" if torch.cuda.is_available() and \
+        dist.get_backend() == "nccl" else "cpu"
+    lens = np.fromiter((len(r) for r in rows), dtype=np.int64, count=len(rows))
+    raw = np.frombuffer(b"".join(rows), dtype=np.uint8).copy()
+    glens = allgather_variable(torch.from_numpy(lens).to(dev)).cpu().numpy()
+    graw = allgather_variable(torch.from_numpy(raw).to(dev)).cpu().numpy() \
+        .tobytes()
+    ends = np.cumsum(glens)
+    merged = sorted({graw[e - l:e] for e, l in zip(ends.tolist(),
+                                                   glens.tolist())})
+    code = {s: i for i, s in enumerate(merged)}
+    remap = np.fromiter((code[r] for r in rows), dtype=np.int64,
+                        count=len(rows))
+    return merged, remap
+
+
 def finalize_q1(rows):
     return q1_finalize(rows)
 

@@ -38,6 +38,18 @@ distinct from the fused query pipelines.
                                    columns at 20 M and 200 M rows, next to
                                    numpy's np.char.find on one core (writes
                                    profiles/text_ops.txt, or PATH)
+  generic_ops_bench.py --textkey [--rows N[,N..]] [--mode-rows N[,N..]]
+                       [--out PATH] [--one N | --one-mode N]
+                                   otbx_text_rank on part-name-shaped columns
+                                   (20 M and 200 M rows, or --rows) and
+                                   shipmode-shaped ones (200 M and 600 M, or
+                                   --mode-rows), ORDER BY p_name and GROUP BY
+                                   l_shipmode end to end, next to numpy's
+                                   np.unique on one core (writes
+                                   profiles/textkey_ops.txt, or PATH). --one N
+                                   / --one-mode N: a single rank of N part
+                                   names / ship modes and nothing else, for a
+                                   kernel tracer
 """
 import ctypes as C
 import os
@@ -1263,8 +1275,191 @@ def bench_text(out_path, sizes):
         f.write("\n".join(lines) + "\n")
 
 
+class _TextRankCall:
+    """otbx_text_rank with the workspace and outputs preallocated."""
+
+    def __init__(self, text):
+        self.node = ex.GpuTextRank([text])
+        self.ts = self.node.textset()
+        self.n = n = len(text)
+        wsb = C.c_size_t(0)
+        lib().otbx_text_rank_workspace_bytes(C.c_int64(n), C.byref(wsb))
+        self.ws_bytes = wsb.value
+        self.ws = torch.empty((wsb.value + 7) // 8, dtype=torch.int64,
+                              device="cuda")
+        self.codes = torch.empty(n, dtype=torch.int64, device="cuda")
+        self.drow = torch.empty(n, dtype=torch.int64, device="cuda")
+        self.nd = torch.zeros(1, dtype=torch.int64, device="cuda")
+        self.rounds = C.c_int32(0)
+        self.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def __call__(self):
+        call("otbx_text_rank", C.byref(self.ts), C.c_void_p(self.ws.data_ptr()),
+             C.c_size_t(self.ws_bytes), C.c_void_p(self.codes.data_ptr()),
+             C.c_void_p(self.drow.data_ptr()), C.c_void_p(self.nd.data_ptr()),
+             C.byref(self.rounds), self.stream)
+
+
+def bench_textkey(out_path, name_sizes, mode_sizes, one=None, one_mode=None):
+    import numpy as np
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    gen = torch.Generator(device="cuda").manual_seed(29)
+    if one is not None or one_mode is not None:
+        # one call for a kernel tracer: no warm-up, no repetition
+        text = _word_rows(P_NAME_WORDS, 5, one, gen) if one is not None \
+            else _word_rows(SHIP_MODES, 1, one_mode, gen)
+        rc = _TextRankCall(text)
+        rc()
+        print(f"rank of {rc.n:_} rows, {len(text.bytes)/rc.n:.1f} B/row: "
+              f"rounds {rc.rounds.value}, {int(rc.nd.item()):_} distinct")
+        return
+
+    say("# tools/generic_ops_bench.py --textkey — best / worst of 5 wall time "
+        "after torch.cuda.synchronize(), one warm-up, all in one process; "
+        "columns staged, workspace and outputs preallocated; every column "
+        "carries a 1 % null mask")
+    say("# otbx_text_rank is synchronous (one int64 read back per round); the "
+        "time is the whole call. Per-kernel split of the rounds: "
+        "profiles/textkey_kernel_trace.txt")
+    say("# extraction pass, algorithmic B per undecided row and round: 8 "
+        "chunk bytes read (or what is left of the row) + 8 offset + 1 mask "
+        "(round 0) + 4 row id and 4 group id (later rounds) read; 4 + 8 + 1 "
+        "(+ 1) written")
+
+    def rank_line(tag, what, text):
+        rc = _TextRankCall(text)
+        b, w = _best_of_5(rc)
+        n, d, r = rc.n, int(rc.nd.item()), rc.rounds.value
+        say(f"({tag}) rows={n:_} {what}: best {b*1e3:9.3f} ms  worst "
+            f"{w*1e3:9.3f} ms (spread {(w-b)/b*100:.1f} %)  "
+            f"{n/b/1e9:.3f} G rows/s; rounds {r}, distinct {d:_}, workspace "
+            f"{rc.ws_bytes/max(n,1):.1f} B/row")
+        return rc
+
+    for n in name_sizes:
+        say()
+        say(f"## part names, {n:_} rows")
+        name = _word_rows(P_NAME_WORDS, 5, n, gen)
+        say(f"# {len(name.bytes)/n:.1f} B/row, {len(name.bytes)/1e9:.2f} GB")
+        rc = rank_line("a", "rank of p_name", name)
+        if n == name_sizes[0]:
+            # numpy on one core over the same non-NULL names, as a
+            # fixed-width array; also the check of the codes at this size
+            nb = len(name.bytes)
+            width = int((name.offs[1:] - name.offs[:-1]).max().item())
+            idx = name.offs[:-1, None] + torch.arange(width, device="cuda")
+            keep = idx < name.offs[1:, None]
+            fixed = torch.where(keep, name.bytes[idx.clamp_(max=nb - 1)],
+                                torch.zeros((), dtype=torch.uint8,
+                                            device="cuda"))
+            valid = name.nulls.cpu().numpy() == 0
+            arr = fixed.cpu().numpy().view(f"S{width}").reshape(-1)[valid]
+            del idx, keep, fixed
+            t0 = time.time()
+            uniq, inv = np.unique(arr, return_inverse=True)
+            th = time.time() - t0
+            codes = rc.codes.cpu().numpy()
+            same = bool(np.array_equal(codes[valid], inv.reshape(-1))) and \
+                bool((codes[~valid] == -1).all()) and \
+                len(uniq) == int(rc.nd.item())
+            say(f"    numpy np.unique(names, return_inverse=True) on one "
+                f"core, S{width} array of the {len(arr):_} non-NULL names: "
+                f"{th*1e3:.0f} ms (one run); codes equal: {same}")
+            assert same
+            del arr, uniq, inv, codes
+
+        # ORDER BY p_name: rank + sort on the codes + gather of the text
+        def order_by():
+            r = name.rank()
+            srt = ex.GpuSort([r.codes[0]], nulls=[name.nulls])
+            srt.BeginCustomScan()
+            perm = srt.ExecCustomScan()
+            srt.EndCustomScan()
+            return name.gather(perm)
+        del rc
+        torch.cuda.empty_cache()
+        b, w = _best_of_5(order_by)
+        say(f"(c) rows={n:_} ORDER BY p_name end to end (rank + GpuSort + text "
+            f"gather, allocations included): best {b*1e3:9.3f} ms  worst "
+            f"{w*1e3:9.3f} ms (spread {(w-b)/b*100:.1f} %)")
+        if n == name_sizes[0]:
+            g = order_by()
+            m = min(n, 1_000_000)
+            head = g.slice(0, m).gather(torch.arange(m, device="cuda"))
+            host = head.to_list()
+            ok = all(x <= y for x, y in zip(host, host[1:])
+                     if x is not None and y is not None)
+            say(f"    first {m:_} output rows ascending on the host: {ok}")
+            assert ok
+            del g, head, host
+        del name
+        torch.cuda.empty_cache()
+
+    for n in mode_sizes:
+        say()
+        say(f"## ship modes, {n:_} rows")
+        mode = _word_rows(SHIP_MODES, 1, n, gen)
+        say(f"# {len(mode.bytes)/n:.1f} B/row")
+        rc = rank_line("b", "rank of l_shipmode", mode)
+        d = rc.drow[:int(rc.nd.item())].clone()
+        assert mode.gather(d).to_list() == \
+            sorted(w.encode() for w in SHIP_MODES)
+        del rc
+        torch.cuda.empty_cache()
+        if n == mode_sizes[0]:
+            ones = torch.ones(n, dtype=torch.float64, device="cuda")
+            res = {}
+
+            def group_by():
+                r = mode.rank()
+                agg = ex.GpuHashAgg(r.codes[0], ones, key_null=mode.nulls)
+                agg.BeginCustomScan()
+                res["rows"] = agg._run()
+                agg.EndCustomScan()
+                res["rank"] = r
+            b, w = _best_of_5(group_by)
+            say(f"(d) rows={n:_} GROUP BY l_shipmode count(*) end to end "
+                f"(rank + hash aggregate, allocations included): best "
+                f"{b*1e3:9.3f} ms  worst {w*1e3:9.3f} ms (spread "
+                f"{(w-b)/b*100:.1f} %)")
+            total = sum(int(g["count_star"]) for g in res["rows"])
+            names = res["rank"].dictionary().to_list()
+            say(f"    groups: {len(res['rows'])} (7 modes + NULL), rows "
+                f"counted {total:_}; dictionary {names}")
+            assert total == n and len(res["rows"]) == 8
+            del ones, res
+        del mode
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def _sizes_arg(flag, default):
+    if flag in sys.argv:
+        return [int(x) for x in sys.argv[sys.argv.index(flag) + 1].split(",")]
+    return default
+
+
 if __name__ == "__main__":
     ex.init_device(0)
+    if "--textkey" in sys.argv:
+        repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        out_path = os.path.join(repo, "profiles", "textkey_ops.txt")
+        if "--out" in sys.argv:
+            out_path = sys.argv[sys.argv.index("--out") + 1]
+        one = _sizes_arg("--one", [None])[0]
+        one_mode = _sizes_arg("--one-mode", [None])[0]
+        bench_textkey(out_path,
+                      _sizes_arg("--rows", [20_000_000, 200_000_000]),
+                      _sizes_arg("--mode-rows", [200_000_000, 600_000_000]),
+                      one=one, one_mode=one_mode)
+        sys.exit(0)
     if "--text" in sys.argv:
         repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         out_path = os.path.join(repo, "profiles", "text_ops.txt")
