@@ -501,7 +501,12 @@ otbx_status otbx_agg_i64_var(const int64_t *keys_dev, const uint8_t *key_null_de
  * Two-key variants join/group on the ROW (k1,k2): a row with EITHER key
  * NULL never matches (strict equality; multi-key hash combine =
  * rotate-left-1 xor, nodeHash.c:2059, restated at 64 bit — parity is on
- * result sets). Overflow contract identical to otbx_join_i64. */
+ * result sets). Overflow contract identical to otbx_join_i64.
+ * nb == 0 and np == 0 are valid: an empty side may pass NULL columns, it
+ * matches nothing, and the other side's rows are emitted as fills where the
+ * join type fills them. OTBX_ERR_INVALID: join_type out of range, ws_dev or
+ * npairs_dev NULL, ws_bytes below otbx_join_ext_workspace_bytes(nb, np),
+ * otbx_join_i64x2 with a NULL second key column on a side that has rows. */
 otbx_status otbx_join_ext_workspace_bytes(int64_t nb, int64_t np,
                                           size_t *bytes);
 otbx_status otbx_join_i64_ext(const int64_t *bkeys_dev,
@@ -526,7 +531,8 @@ otbx_status otbx_join_i64x2(const int64_t *bk1_dev, const uint8_t *bn1_dev,
  * NULL==NULL grouping (execGrouping.c:295,:525); aggregates as
  * otbx_agg_i64. groups_dev capacity = n rows; *ngroups_dev receives the
  * group count; emission order is arbitrary (hash-table order, as the
- * reference's simplehash iteration). */
+ * reference's simplehash iteration). n == 0 gives zero groups and may pass
+ * NULL columns; a NULL key column with n > 0 is OTBX_ERR_INVALID. */
 typedef struct {
     int64_t key1;
     int64_t key2;
@@ -556,7 +562,12 @@ otbx_status otbx_agg_i64x2(const int64_t *k1_dev, const uint8_t *k1null_dev,
  * N key values — the reference's hash table stores the representative
  * tuple the same way (execGrouping.c firstTuple); the caller reads the key
  * values back through the index. Joins emit (bidx, pidx) pairs exactly as
- * otbx_join_i64_ext (same join_type codes, fills and overflow contract). */
+ * otbx_join_i64_ext (same join_type codes, fills and overflow contract).
+ * otbx_agg_i64n with n == 0 gives zero groups; otbx_join_i64n with nb == 0
+ * or np == 0 treats that side as empty. The columns of an empty input may be
+ * NULL; nkeys must still be 1..OTBX_MAX_KEYS and equal on both join sides.
+ * A NULL key (or, for the aggregate, value) column with a row count > 0 is
+ * OTBX_ERR_INVALID. */
 #define OTBX_MAX_KEYS 8
 typedef struct {
     int32_t nkeys;                           /* 1..OTBX_MAX_KEYS */
@@ -596,7 +607,9 @@ otbx_status otbx_join_i64n(const otbx_keyset *bks, int64_t nb,
  * and cannot overflow, int8_sum :6206). Values are scaled-decimal int64
  * (e.g. NUMERIC(15,2) money in cents); the emitted two's-complement
  * 128-bit sum is EXACT, so parity with the reference is bit-exact —
- * no float tolerance. groups_dev capacity = n. */
+ * no float tolerance. groups_dev capacity = n. n == 0 gives zero groups and
+ * may pass NULL columns; NULL keys_dev or vals_dev with n > 0 is
+ * OTBX_ERR_INVALID. */
 typedef struct {
     int64_t key;
     int64_t count_star;

@@ -6762,7 +6762,8 @@ otbx_status otbx_join_i64x2(const int64_t *bk1, const uint8_t *bn1,
                             int64_t *out_b, int64_t *out_p, int64_t cap_pairs,
                             int64_t *npairs_dev, void *stream)
 {
-    if (!bk2 || !pk2)
+    /* an empty side may carry NULL columns (the otbx_sort_perm rule) */
+    if ((nb > 0 && !bk2) || (np > 0 && !pk2))
         return OTBX_ERR_INVALID;
     return joinx_run(bk1, bn1, bk2, bn2, nb, pk1, pn1, pk2, pn2, np, 2,
                      join_type, ws, ws_bytes, out_b, out_p, cap_pairs,
@@ -6785,7 +6786,7 @@ otbx_status otbx_agg_i64x2(const int64_t *k1, const uint8_t *k1null,
                            otbx_agg2_group *groups_dev, int64_t *ngroups_dev,
                            void *stream)
 {
-    if (!ws || !ngroups_dev || !k1 || !k2)
+    if (!ws || !ngroups_dev || (n > 0 && (!k1 || !k2)))
         return OTBX_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     int64_t cap = jx_cap_for(n);
@@ -6947,7 +6948,7 @@ otbx_status otbx_agg_i64_dec(const int64_t *keys, const uint8_t *knull,
                              otbx_dec_group *groups_dev, int64_t *ngroups_dev,
                              void *stream)
 {
-    if (!ws || !ngroups_dev || !keys || !vals)
+    if (!ws || !ngroups_dev || (n > 0 && (!keys || !vals)))
         return OTBX_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     int64_t cap = jx_cap_for(n);
@@ -7250,11 +7251,13 @@ __global__ void k_joinn_fill_build(const otbx_keyset ks, int64_t nb,
 
 extern "C" {
 
-static bool keyset_ok(const otbx_keyset *ks)
+/* n = the row count the keyset's columns hold: an empty side may carry NULL
+ * columns (the otbx_sort_perm rule), nkeys is checked either way */
+static bool keyset_ok(const otbx_keyset *ks, int64_t n)
 {
     if (!ks || ks->nkeys < 1 || ks->nkeys > OTBX_MAX_KEYS)
         return false;
-    for (int c = 0; c < ks->nkeys; c++)
+    for (int c = 0; n > 0 && c < ks->nkeys; c++)
         if (!ks->keys[c])
             return false;
     return true;
@@ -7272,7 +7275,7 @@ otbx_status otbx_agg_i64n(const otbx_keyset *ks, const double *vals,
                           size_t ws_bytes, otbx_aggn_group *groups_dev,
                           int64_t *ngroups_dev, void *stream)
 {
-    if (!keyset_ok(ks) || !ws || !ngroups_dev || !vals)
+    if (!keyset_ok(ks, n) || !ws || !ngroups_dev || (n > 0 && !vals))
         return OTBX_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     int64_t cap = jx_cap_for(n);
@@ -7314,7 +7317,8 @@ otbx_status otbx_join_i64n(const otbx_keyset *bks, int64_t nb,
                            int64_t *out_b, int64_t *out_p, int64_t cap_pairs,
                            int64_t *npairs_dev, void *stream)
 {
-    if (!keyset_ok(bks) || !keyset_ok(pks) || bks->nkeys != pks->nkeys ||
+    if (!keyset_ok(bks, nb) || !keyset_ok(pks, np) ||
+        bks->nkeys != pks->nkeys ||
         join_type < 0 || join_type > 5 || !ws || !npairs_dev)
         return OTBX_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
