@@ -42,6 +42,12 @@
  *                            ExecWindowAgg (executor/nodeWindowAgg.c) with
  *                            row_number / rank / dense_rank and count / sum
  *                            over the default frame (windowfuncs.c:82-118)
+ *   otbx_window_frame      — the rest of that node's PG10-era frame model:
+ *                            explicit ROWS / RANGE frames (row_is_in_frame,
+ *                            nodeWindowAgg.c:1472) with lag / lead / ntile
+ *                            (windowfuncs.c:231-378), first / last /
+ *                            nth_value (WinGetFuncArgInFrame :3368) and
+ *                            count / sum / min / max over the frame
  *   otbx_group_agg         — the Agg node's sorted strategies over that
  *                            sorted input: AGG_SORTED / AGG_PLAIN
  *                            (agg_retrieve_direct, nodeAgg.c:2249) with
@@ -109,6 +115,11 @@
  *                            LIKE with a % before the pattern's last token,
  *                            the shapes where staging measured faster
  *                            (tests run both paths; A/B)
+ *   OTBX_WIN_FRAME_DIRECT=N — otbx_window_frame reduces a bounded ROWS frame
+ *                            of at most N positions by a per-row loop and a
+ *                            wider one by segmented scans; 0 = never the
+ *                            loop. Unset: the measured default (tests run
+ *                            both paths on one input; A/B)
  */
 #ifndef OTBX_H
 #define OTBX_H
@@ -777,6 +788,123 @@ otbx_status otbx_window(const otbx_sortspec *spec, int32_t npart,
                         const double *vals_dev, const uint8_t *val_null_dev,
                         void *ws_dev, size_t ws_bytes,
                         const otbx_window_out *out, void *stream);
+
+/* ---- GPU WindowAgg frames: lag / lead, ntile, value functions and
+ * aggregates over an explicit ROWS or RANGE frame ----
+ * The rest of ExecWindowAgg for the reference's frame model: one call serves
+ * ONE window specification and ONE frame and evaluates up to
+ * OTBX_MAX_WINCALLS function calls that share them. spec, npart, perm_dev
+ * (NULL = identity; entries are clamped) and n mean exactly what they mean
+ * for otbx_window, and partition / peer equality is the sort's normalised
+ * key. otbx_window is unchanged; this entry point stands beside it.
+ *
+ * FRAME (row_is_in_frame / update_frameheadpos, nodeWindowAgg.c:1472-1560)
+ *   For sorted position j in partition [ps, pe] with peer group [gs, ge] the
+ *   frame is [lo, hi], empty when lo > hi.
+ *   ROWS:  lo = ps (UNBOUNDED) or max(ps, j + start_off);
+ *          hi = pe (UNBOUNDED) or min(pe, j + end_off); CURRENT is offset 0.
+ *   RANGE: lo = ps (UNBOUNDED) or gs (CURRENT); hi = pe (UNBOUNDED) or ge
+ *          (CURRENT). OTBX_FB_OFFSET under RANGE is OTBX_ERR_INVALID.
+ *   Offsets are any int64; j + off saturates, so INT64_MIN / INT64_MAX mean
+ *   "before / after everything". The parser's shape restrictions
+ *   (gram.y:17275-17316: no "UNBOUNDED FOLLOWING" start, no start after the
+ *   end, ...) are NOT enforced: a shape such as "CURRENT ROW .. 1 PRECEDING"
+ *   simply gives empty frames.
+ *
+ * FUNCTIONS — col / nulls are indexed by INPUT row and read through perm;
+ * every output is indexed by SORTED POSITION.
+ *   NTILE(param)       int32 (window_ntile, windowfuncs.c:231): with T rows
+ *                      in the partition, q = T / param, r = T % param and
+ *                      0-based row i: i + 1 if q == 0; i/(q+1) + 1 if
+ *                      i < r*(q+1); else r + (i - r*(q+1))/q + 1.
+ *   LAG / LEAD(param)  leadlag_common (:306) with a constant signed offset
+ *                      (a negative lag is a lead); the frame is ignored. The
+ *                      source position j -/+ param inside the partition
+ *                      gives that row's value and null flag; outside it the
+ *                      default: def_i (I64 / I32 / U8) or def_f (F64), or
+ *                      NULL when def_isnull is set.
+ *   FIRST_VALUE / LAST_VALUE / NTH_VALUE(param >= 1)
+ *                      WinGetFuncArgInFrame (nodeWindowAgg.c:3368): the row
+ *                      at lo, hi or lo + param - 1; NULL when the frame is
+ *                      empty or that position is past hi. A NULL value is
+ *                      returned as NULL (no IGNORE NULLS).
+ *   COUNT_STAR / COUNT / SUM / MIN / MAX over the frame: the result types,
+ *                      strictness, int128 SUM(I64) encoding and float MIN /
+ *                      MAX rules (bit pattern of the chosen row, the later
+ *                      row of the frame wins a tie) of otbx_group_agg. An
+ *                      empty frame, or one without a non-NULL input, gives
+ *                      out_null = 1 and value 0 for SUM / MIN / MAX, and 0
+ *                      for the counts.
+ *   Wherever a result is NULL the value stored is 0. out_null is required
+ *   for every function except NTILE and the two counts and must be NULL for
+ *   those; out_hi is required for SUM over I64 and must be NULL otherwise.
+ *
+ * NUMERICS OF SUM(F64): float8 sum has no inverse transition, so the
+ *   reference re-aggregates every frame left to right (eval_windowaggregates,
+ *   nodeWindowAgg.c:919-933). Here the reduction is SEGMENTED: no differences
+ *   of float prefix sums and no float atomics, so an Inf or NaN never leaks
+ *   into another frame or partition. With both bounds OFFSET / CURRENT under
+ *   ROWS and end_off - start_off + 1 at most the direct cut-over, the frame's
+ *   non-NULL values are added left to right: BIT-EQUAL to the reference.
+ *   Otherwise (an unbounded side, RANGE, or a wider frame) the sum is a
+ *   tree: within m*u*sum|x| / (1 - m*u), m = non-NULL terms - 1, u = 2^-53
+ *   (otbx_window's clause), bit-equal wherever every order is exact. Results
+ *   are bit-identical from run to run. Overflow of finite inputs is not
+ *   detected.
+ *
+ * DIRECT CUT-OVER: *width of otbx_window_frame_direct_default (128) is the widest
+ *   bounded ROWS frame reduced by a per-row loop; wider ones take two
+ *   segmented scans whatever their width. OTBX_WIN_FRAME_DIRECT=N overrides
+ *   it at call time (0 = never direct).
+ *
+ * Stream-ordered, no host synchronisation, nothing cached (otbx_finish has
+ * nothing to release). Checked before any HIP call, each returning
+ * OTBX_ERR_INVALID: spec, frame or calls NULL; ncalls outside 1..8; nkeys,
+ * npart, key type / flags, key columns and n as for otbx_window; units or a
+ * bound kind out of range, or OFFSET under RANGE; func or type of a call out
+ * of range; out NULL; col NULL with n > 0 for anything but NTILE /
+ * COUNT_STAR / COUNT; the out_null / out_hi rules above; NTILE param <= 0,
+ * NTH_VALUE param < 1, a LAG / LEAD param outside int32; ws_bytes below
+ * otbx_window_frame_workspace_bytes(n, ncalls), ws_dev NULL or not 16-byte
+ * aligned. n == 0 is valid and writes nothing.
+ * otbx_window_frame_workspace_bytes is pure host code and monotone in both
+ * arguments. sizeof(otbx_frame) == 32, sizeof(otbx_wincall) == 80. */
+enum { OTBX_FRAME_ROWS = 0, OTBX_FRAME_RANGE = 1 };
+enum { OTBX_FB_UNBOUNDED = 0,  /* start: UNBOUNDED PRECEDING; end: UNBOUNDED FOLLOWING */
+       OTBX_FB_CURRENT   = 1,  /* CURRENT ROW; under RANGE: first / last peer          */
+       OTBX_FB_OFFSET    = 2 };/* ROWS only: position + off; off<0 PRECEDING, >0 FOLLOWING */
+typedef struct {
+    int32_t units, start_kind, end_kind, _pad;
+    int64_t start_off, end_off;
+} otbx_frame;
+
+enum { OTBX_WF_NTILE = 0, OTBX_WF_LAG, OTBX_WF_LEAD, OTBX_WF_FIRST_VALUE,
+       OTBX_WF_LAST_VALUE, OTBX_WF_NTH_VALUE, OTBX_WF_COUNT_STAR,
+       OTBX_WF_COUNT, OTBX_WF_SUM, OTBX_WF_MIN, OTBX_WF_MAX };
+#define OTBX_MAX_WINCALLS 8
+typedef struct {
+    const void    *col;        /* input column of `type`, indexed by INPUT row  */
+    const uint8_t *nulls;      /* byte per row, nonzero = NULL; may be NULL      */
+    void          *out;        /* n entries, indexed by SORTED position          */
+    int64_t       *out_hi;     /* SUM over I64 only: high words                  */
+    uint8_t       *out_null;   /* see above                                      */
+    int64_t        param;      /* NTILE: buckets; LAG/LEAD: offset; NTH_VALUE: n */
+    int64_t        def_i;      /* LAG/LEAD default for I64 / I32 / U8            */
+    double         def_f;      /* LAG/LEAD default for F64                       */
+    int32_t        def_isnull; /* LAG/LEAD: the default is NULL                  */
+    int32_t        func;       /* OTBX_WF_*                                      */
+    int32_t        type;       /* OTBX_SORT_I64 / F64 / I32 / U8                 */
+    int32_t        _pad;
+} otbx_wincall;                /* 80 B */
+
+otbx_status otbx_window_frame_direct_default(int64_t *width);
+otbx_status otbx_window_frame_workspace_bytes(int64_t n, int32_t ncalls,
+                                              size_t *bytes);
+otbx_status otbx_window_frame(const otbx_sortspec *spec, int32_t npart,
+                              const int64_t *perm_dev, int64_t n,
+                              const otbx_frame *frame,
+                              const otbx_wincall *calls, int32_t ncalls,
+                              void *ws_dev, size_t ws_bytes, void *stream);
 
 /* ---- GPU GroupAggregate: count / sum / min / max per run of equal keys ----
  * The sorted-input aggregation strategy of the Agg node (AGG_SORTED, and

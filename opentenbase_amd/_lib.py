@@ -106,6 +106,34 @@ class WindowOutDev(C.Structure):
                 ("sum_isnull", C.c_void_p), ("part_rows", C.c_void_p)]
 
 
+FRAME_ROWS, FRAME_RANGE = 0, 1               # OTBX_FRAME_*
+FB_UNBOUNDED, FB_CURRENT, FB_OFFSET = 0, 1, 2   # OTBX_FB_*
+WIN_FUNCS = {"ntile": 0, "lag": 1, "lead": 2, "first_value": 3,
+             "last_value": 4, "nth_value": 5, "count_star": 6, "count": 7,
+             "sum": 8, "min": 9, "max": 10}     # OTBX_WF_*
+MAX_WINCALLS = 8                                # OTBX_MAX_WINCALLS
+
+
+class FrameDev(C.Structure):
+    """otbx_frame (include/otbx.h): one window frame, 32 bytes."""
+    _fields_ = [("units", C.c_int32), ("start_kind", C.c_int32),
+                ("end_kind", C.c_int32), ("_pad", C.c_int32),
+                ("start_off", C.c_int64), ("end_off", C.c_int64)]
+
+
+class WinCallDev(C.Structure):
+    """otbx_wincall: one function call of a window-frame list, 80 bytes."""
+    _fields_ = [("col", C.c_void_p), ("nulls", C.c_void_p),
+                ("out", C.c_void_p), ("out_hi", C.c_void_p),
+                ("out_null", C.c_void_p),
+                ("param", C.c_int64), ("def_i", C.c_int64),
+                ("def_f", C.c_double), ("def_isnull", C.c_int32),
+                ("func", C.c_int32), ("type", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
+assert C.sizeof(FrameDev) == 32 and C.sizeof(WinCallDev) == 80
+
 AGG_FUNCS = {"count_star": 0, "count": 1, "sum": 2, "min": 3, "max": 4}
 MAX_AGGS = 8   # OTBX_MAX_AGGS
 
@@ -229,6 +257,10 @@ def lib():
         _lib.otbx_q9_workspace_bytes.argtypes = [i64, i64, i64, u32, szp]
         _lib.otbx_sort_workspace_bytes.argtypes = [i64, C.c_int32, i64, szp]
         _lib.otbx_window_workspace_bytes.argtypes = [i64, szp]
+        _lib.otbx_window_frame_workspace_bytes.argtypes = [i64, C.c_int32,
+                                                           szp]
+        _lib.otbx_window_frame_direct_default.argtypes = [
+            C.POINTER(C.c_int64)]
         _lib.otbx_filter_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_group_agg_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_text_gather_workspace_bytes.argtypes = [i64, szp]
@@ -272,6 +304,8 @@ EXPORTED_SYMBOLS = [
     "otbx_join_i64n_workspace_bytes", "otbx_join_i64n",
     "otbx_sort_workspace_bytes", "otbx_sort_perm",
     "otbx_window_workspace_bytes", "otbx_window",
+    "otbx_window_frame_direct_default", "otbx_window_frame_workspace_bytes",
+    "otbx_window_frame",
     "otbx_filter_workspace_bytes", "otbx_filter_sel",
     "otbx_project",
     "otbx_group_agg_workspace_bytes", "otbx_group_agg",

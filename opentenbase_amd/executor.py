@@ -16,11 +16,14 @@ import math
 
 import torch
 
-from ._lib import (AGG_FUNCS, MAX_AGGS, MAX_TEXT_CONST, MAX_TEXT_RANK_COLS,
-                   TEXT_ENCODINGS, TXT_OPS, AggCallsDev, CustomerDev, ExprDev,
+from ._lib import (AGG_FUNCS, FB_CURRENT, FB_OFFSET, FB_UNBOUNDED,
+                   FRAME_RANGE, FRAME_ROWS, MAX_AGGS, MAX_TEXT_CONST,
+                   MAX_TEXT_RANK_COLS, MAX_WINCALLS, TEXT_ENCODINGS, TXT_OPS,
+                   WIN_FUNCS, AggCallsDev, CustomerDev, ExprDev, FrameDev,
                    KeysetDev, LineitemDev, OrdersDev, OtbxError, PartDev,
                    Q1_DICT_MAX, Q1CodeDesc, QualDev, SortSpecDev, TextColDev,
-                   TextPredDev, TextSetDev, WindowOutDev, call, check, lib)
+                   TextPredDev, TextSetDev, WinCallDev, WindowOutDev, call,
+                   check, lib)
 
 Q1_SLOT_ORDER = [(b"A", b"F"), (b"A", b"O"), (b"N", b"F"),
                  (b"N", b"O"), (b"R", b"F"), (b"R", b"O")]
@@ -904,6 +907,244 @@ def cume_dist(count_star, part_rows):
     out = np.asarray(count_star, dtype=np.float64) / \
         np.asarray(part_rows, dtype=np.float64)
     return float(out) if out.ndim == 0 else out
+
+
+def _frame_bound(b, units, what):
+    if b is None:
+        return FB_UNBOUNDED, 0
+    if isinstance(b, str):
+        if b != "current":
+            raise OtbxError(3, f"frame: unknown {what} bound {b!r}")
+        return FB_CURRENT, 0
+    b = int(b)
+    if b == 0:
+        return FB_CURRENT, 0
+    if units == FRAME_RANGE:
+        raise OtbxError(3, "frame: RANGE takes no offset bound")
+    if not -2**63 <= b < 2**63:
+        raise OtbxError(3, "frame: offset outside int64")
+    return FB_OFFSET, b
+
+
+def _frame(units, start, end):
+    f = FrameDev()
+    f.units = units
+    f.start_kind, f.start_off = _frame_bound(start, units, "start")
+    f.end_kind, f.end_off = _frame_bound(end, units, "end")
+    return f
+
+
+def rows_between(start, end):
+    """ROWS BETWEEN start AND end as an otbx_frame. A bound is None
+    (UNBOUNDED PRECEDING as start, UNBOUNDED FOLLOWING as end), 0 or
+    "current" (CURRENT ROW), or a signed row offset: -2 is 2 PRECEDING, 3 is
+    3 FOLLOWING."""
+    return _frame(FRAME_ROWS, start, end)
+
+
+def range_between(start, end):
+    """RANGE BETWEEN start AND end: each bound None (unbounded) or 0 /
+    "current" (the first / last peer of the current row)."""
+    return _frame(FRAME_RANGE, start, end)
+
+
+def window_frame_direct_default():
+    """The widest bounded ROWS frame otbx_window_frame reduces by its per-row
+    loop when OTBX_WIN_FRAME_DIRECT is unset."""
+    w = C.c_int64(0)
+    check(lib().otbx_window_frame_direct_default(C.byref(w)),
+          "otbx_window_frame_direct_default")
+    return w.value
+
+
+class GpuWindowFrame(CustomScanState):
+    """The WindowAgg node (nodeWindowAgg.c) for one window specification
+    OVER (PARTITION BY partition_by ORDER BY order_by <frame>) and up to 8
+    function calls that share it. frame comes from rows_between /
+    range_between (default: RANGE UNBOUNDED PRECEDING .. CURRENT ROW). A call
+    is one of
+        ("ntile", buckets)
+        ("lag" | "lead", col[, nulls[, offset = 1[, default = None]]])
+        ("first_value" | "last_value", col[, nulls])
+        ("nth_value", col, nulls, n)
+        ("count_star",) | ("count", col[, nulls])
+        ("sum" | "min" | "max", col[, nulls])
+    with col a device tensor of dtype int64, float64, int32 or uint8 and
+    nulls a uint8 mask (nonzero = NULL) or None; a lag / lead default of None
+    is NULL. Keys are taken as GpuWindowAgg takes them. Runs GpuSort on the
+    combined key list (skipped with zero keys: perm = NULL), then
+    otbx_window_frame. Yields ONE tuple, a dict indexed by sorted position:
+        "calls"  [(values, nulls or None)] in call order; an int64 SUM
+                 yields (lo, hi, nulls) as GpuGroupAgg does (int128_sums)
+        <name>   the same tuple under the call's function name (the first
+                 call of that name)
+        "perm"   the sort's permutation
+    Contract in include/otbx.h (otbx_window_frame)."""
+
+    def __init__(self, partition_by, order_by, descending=None,
+                 nulls_first=None, part_nulls=None, order_nulls=None,
+                 frame=None, calls=(), n=None):
+        super().__init__()
+        self.partition_by, self.order_by = list(partition_by), list(order_by)
+        self.keys = self.partition_by + self.order_by
+        npart, nord = len(self.partition_by), len(self.order_by)
+        if npart + nord > 8:
+            raise OtbxError(3, "window frame: at most 8 keys")
+        pn = [None] * npart if part_nulls is None else list(part_nulls)
+        on = [None] * nord if order_nulls is None else list(order_nulls)
+        if len(pn) != npart or len(on) != nord:
+            raise OtbxError(3, "window frame: one nulls entry per key")
+        self.nulls = pn + on
+        self.flags = sort_flags(npart) + \
+            sort_flags(nord, descending, nulls_first)
+        for k in self.keys:
+            if k.dtype not in _SORT_TYPE:
+                raise OtbxError(
+                    3, f"window frame: unsupported key dtype {k.dtype}")
+        self.frame = range_between(None, 0) if frame is None else frame
+        if not isinstance(self.frame, FrameDev):
+            raise OtbxError(3, "window frame: frame comes from rows_between "
+                               "/ range_between")
+        self.calls = []
+        for c in calls:
+            c = tuple(c)
+            if not c or c[0] not in WIN_FUNCS:
+                raise OtbxError(3, f"window frame: unknown function {c[:1]}")
+            func = c[0]
+            col = nl = default = None
+            param = 0
+            if func == "ntile":
+                if len(c) != 2:
+                    raise OtbxError(3, "window frame: ntile takes buckets")
+                param = int(c[1])
+            else:
+                col = c[1] if len(c) > 1 else None
+                nl = c[2] if len(c) > 2 else None
+                if func in ("lag", "lead"):
+                    param = int(c[3]) if len(c) > 3 else 1
+                    default = c[4] if len(c) > 4 else None
+                elif func == "nth_value":
+                    if len(c) != 4:
+                        raise OtbxError(
+                            3, "window frame: nth_value takes col, nulls, n")
+                    param = int(c[3])
+            if func not in ("ntile", "count_star", "count") and col is None:
+                raise OtbxError(3, f"window frame: {func} needs a column")
+            if col is not None and col.dtype not in _SORT_TYPE:
+                raise OtbxError(
+                    3, f"window frame: unsupported dtype {col.dtype}")
+            self.calls.append((func, col, nl, param, default))
+        if not 1 <= len(self.calls) <= MAX_WINCALLS:
+            raise OtbxError(3, "window frame: 1..8 calls")
+        if n is None:
+            cols = self.keys + [c[1] for c in self.calls if c[1] is not None]
+            if not cols:
+                raise OtbxError(3, "window frame: no column to size by — "
+                                   "pass n")
+            n = len(cols[0])
+        self.n = int(n)
+        for k in self.keys:
+            if len(k) != self.n:
+                raise OtbxError(3, "window frame: key columns differ in "
+                                   "length")
+        self.perm = None
+        self.sort_ms = None
+        self.window_ms = None
+
+    def _run(self):
+        L = lib()
+        n = self.n
+        self.sort_ms = 0.0
+        perm = None
+        if self.keys:
+            srt = GpuSort(self.keys, nulls=self.nulls)
+            srt.flags = list(self.flags)
+            srt.BeginCustomScan()
+            perm = srt.ExecCustomScan()
+            srt.EndCustomScan()
+            self.sort_ms = srt.sort_ms
+            sp = srt.spec()
+        else:
+            sp = SortSpecDev()
+            sp.nkeys = 0
+        ws_bytes = C.c_size_t(0)
+        check(L.otbx_window_frame_workspace_bytes(
+            C.c_int64(n), C.c_int32(len(self.calls)), C.byref(ws_bytes)),
+            "otbx_window_frame_workspace_bytes")
+        ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8,
+                         device="cuda")
+        cap = max(n, 1)
+
+        def new(dtype):
+            return torch.empty(cap, dtype=dtype, device="cuda")
+
+        # an empty tensor has no address: with no rows, hand the argument
+        # check a placeholder so that "column given" stays visible to it
+        hold = torch.zeros(1, dtype=torch.int64, device="cuda")
+        calls = (WinCallDev * MAX_WINCALLS)()
+        outs = []
+        for i, (func, col, nl, param, default) in enumerate(self.calls):
+            wc = calls[i]
+            wc.func = WIN_FUNCS[func]
+            wc.type = _SORT_TYPE[col.dtype] if col is not None else 0
+            wc.param = param
+            if col is not None:
+                wc.col = col.data_ptr() if n > 0 else hold.data_ptr()
+            wc.nulls = nl.data_ptr() if nl is not None and n > 0 else None
+            wc.def_isnull = 1 if default is None else 0
+            if default is not None:
+                if col.dtype == torch.float64:
+                    wc.def_f = float(default)
+                else:
+                    wc.def_i = int(default)
+            if func == "ntile":
+                o = (new(torch.int32),)
+            elif func in ("count_star", "count"):
+                o = (new(torch.int64),)
+            elif func == "sum" and col.dtype == torch.int64:
+                o = (new(torch.int64), new(torch.int64), new(torch.uint8))
+                wc.out_hi = o[1].data_ptr()
+            elif func == "sum":
+                o = (new(torch.float64 if col.dtype == torch.float64
+                         else torch.int64), new(torch.uint8))
+            else:
+                o = (new(col.dtype), new(torch.uint8))
+            wc.out = o[0].data_ptr()
+            if len(o) > 1:
+                wc.out_null = o[-1].data_ptr()
+            outs.append(o)
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        call("otbx_window_frame", C.byref(sp),
+             C.c_int32(len(self.partition_by)),
+             C.c_void_p(perm.data_ptr()) if perm is not None and n > 0
+             else None,
+             C.c_int64(n), C.byref(self.frame), calls,
+             C.c_int32(len(self.calls)), C.c_void_p(ws.data_ptr()),
+             C.c_size_t(ws_bytes.value), _stream())
+        ev1.record()
+        ev1.synchronize()
+        self.window_ms = ev0.elapsed_time(ev1)
+        self.perm = perm if perm is not None else \
+            torch.arange(n, dtype=torch.int64, device="cuda")
+        res = {"calls": [tuple(t[:n] for t in o) if len(o) > 1
+                         else (o[0][:n], None) for o in outs]}
+        for (func, *_), r in zip(self.calls, res["calls"]):
+            res.setdefault(func, r)
+        res["perm"] = self.perm
+        return [res]
+
+    def gather(self, col):
+        """col in sorted order (runs the node if it has not run)."""
+        if self.perm is None:
+            self._run()
+        return gather(col, self.perm)
+
+    def explain(self):
+        if self.window_ms is None:
+            return None
+        return {"sort": self.sort_ms, "window_frame": self.window_ms}
 
 
 class GpuGroupAgg(CustomScanState):

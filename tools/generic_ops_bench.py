@@ -719,6 +719,213 @@ def bench_groupagg(out_path, n=600_000_000):
         f.write("\n".join(lines) + "\n")
 
 
+class _FrameCall:
+    """otbx_window_frame on an already sorted permutation (or perm = NULL),
+    buffers allocated once. calls: (func, col, param) with col a device
+    tensor or None"""
+
+    def __init__(self, srt, npart, frame, calls):
+        from opentenbase_amd._lib import WIN_FUNCS, WinCallDev
+        self.n, self.npart, self.frame = srt.n, npart, frame
+        self.spec, self.perm, self.stream = srt.spec, srt.perm, srt.stream
+        wsb = C.c_size_t(0)
+        lib().otbx_window_frame_workspace_bytes(
+            C.c_int64(self.n), C.c_int32(len(calls)), C.byref(wsb))
+        self.wsb = wsb.value
+        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device="cuda")
+        self.calls = (WinCallDev * 8)()
+        self.ncalls = len(calls)
+        self.outs, self.keep = [], []
+        types = {torch.int64: 0, torch.float64: 1, torch.int32: 2,
+                 torch.uint8: 3}
+        for i, (func, col, param) in enumerate(calls):
+            wc = self.calls[i]
+            wc.func, wc.param, wc.def_isnull = WIN_FUNCS[func], param, 1
+            if col is not None:
+                wc.col, wc.type = col.data_ptr(), types[col.dtype]
+                self.keep.append(col)
+            dt = torch.int32 if func == "ntile" else (
+                torch.int64 if func in ("count", "count_star") or
+                col.dtype != torch.float64 else torch.float64)
+            o = [torch.empty(self.n, dtype=dt, device="cuda")]
+            wc.out = o[0].data_ptr()
+            if func not in ("ntile", "count", "count_star"):
+                o.append(torch.empty(self.n, dtype=torch.uint8, device="cuda"))
+                wc.out_null = o[-1].data_ptr()
+                if func == "sum" and col.dtype == torch.int64:
+                    o.append(torch.empty(self.n, dtype=torch.int64,
+                                         device="cuda"))
+                    wc.out_hi = o[-1].data_ptr()
+            self.outs.append(o)
+
+    def __call__(self):
+        call("otbx_window_frame", C.byref(self.spec), C.c_int32(self.npart),
+             C.c_void_p(self.perm.data_ptr()) if self.perm is not None
+             else None, C.c_int64(self.n), C.byref(self.frame), self.calls,
+             C.c_int32(self.ncalls), C.c_void_p(self.ws.data_ptr()),
+             C.c_size_t(self.wsb), self.stream)
+
+
+# algorithmic bytes per row of the kernels of one otbx_window_frame call
+# (DESIGN.md §8n): the bounds pass gathers perm and key and writes / reads
+# the flag byte and two int64 bound arrays; a position function reads the two
+# bounds, gathers perm + value and writes value + null byte; an aggregate
+# gathers perm + value into 9 staged bytes, then either loops over them
+# (direct: staged bytes read once from memory, the rest from cache) or runs
+# one scan (staged bytes read twice, 12 state bytes written) per direction
+# and reads the bounds and one or two states back
+_WF_BOUNDS = 8 + 8 + 2 + 2 * 8
+_WF_POS = 2 * 8 + 8 + 8 + 8 + 1
+_WF_NTILE = 2 * 8 + 4
+_WF_GATHER = 8 + 8 + 9
+_WF_DIRECT = 2 * 8 + 9 + 8 + 1
+_WF_SCAN = 2 * 9 + 2 + 12
+_WF_FINAL1 = 2 * 8 + 12 + 8 + 1
+_WF_FINAL2 = 2 * 8 + 2 * 12 + 8 + 1
+
+
+def bench_winframe(out_path, n=600_000_000, ab_n=200_000_000):
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    def rate(nbytes, t):
+        tbs = nbytes / t / 1e12
+        return (f"{nbytes/1e9:.1f} GB algorithmic  {tbs:5.2f} TB/s = "
+                f"{tbs*1e12/COPY_CEILING*100:4.1f} % of the 6.29 TB/s copy "
+                f"ceiling")
+
+    say("# tools/generic_ops_bench.py --winframe — best / worst of 5 wall "
+        "time after torch.cuda.synchronize(), columns staged")
+    say("# OVER (PARTITION BY one i64 key), f64 values; the sort and "
+        "otbx_window_frame are timed apart")
+    dflt = ex.window_frame_direct_default()
+    g = torch.Generator(device="cuda").manual_seed(13)
+
+    # ---- the direct cut-over: per-row loop against the two scans ----
+    say(f"# cut-over A/B at n={ab_n:_}, 1_000_000 partitions, sum f64 over "
+        f"ROWS (W-1) PRECEDING .. CURRENT ROW, perm given; "
+        f"OTBX_WIN_FRAME_DIRECT=4097 (loop) against =0 (scans)")
+    key = torch.randint(0, 1_000_000, (ab_n,), dtype=torch.int64,
+                        device="cuda", generator=g)
+    vals = torch.randint(-1000, 1001, (ab_n,), dtype=torch.int64,
+                         device="cuda", generator=g).to(torch.float64)
+    srt = _SortCall([key], [False])
+    srt()
+    torch.cuda.synchronize()
+    for w in (2, 4, 8, 16, 32, 64, 128, 256):
+        fc = _FrameCall(srt, 1, ex.rows_between(-(w - 1), 0),
+                        [("sum", vals, 0)])
+        os.environ["OTBX_WIN_FRAME_DIRECT"] = "4097"
+        lb, lw = _best_of_5(fc)
+        loop_out = fc.outs[0][0].clone()
+        os.environ["OTBX_WIN_FRAME_DIRECT"] = "0"
+        sb, sw = _best_of_5(fc)
+        same = bool(torch.equal(loop_out, fc.outs[0][0]))
+        del os.environ["OTBX_WIN_FRAME_DIRECT"]
+        say(f"  W={w:4d}: loop best {lb*1e3:7.2f} ms worst {lw*1e3:7.2f} ms; "
+            f"scans best {sb*1e3:7.2f} ms worst {sw*1e3:7.2f} ms; loop / "
+            f"scans {lb/sb:.2f}; equal results (integer-valued): {same}")
+        del fc, loop_out
+        torch.cuda.empty_cache()
+    say(f"# compiled default cut-over: {dflt}")
+    del key, vals, srt
+    torch.cuda.empty_cache()
+
+    # ---- the operator at scale ----
+    v64 = torch.randint(-1000, 1001, (n,), dtype=torch.int64, device="cuda",
+                        generator=g)
+    vals = v64.to(torch.float64)
+    del v64
+    cases = (
+        ("lag(1)", ex.rows_between(None, 0), [("lag", vals, 1)],
+         _WF_BOUNDS + _WF_POS),
+        ("ntile(4)", ex.rows_between(None, 0), [("ntile", None, 4)],
+         _WF_BOUNDS + _WF_NTILE),
+        ("ROWS -6..0 sum + count", ex.rows_between(-6, 0),
+         [("sum", vals, 0), ("count", vals, 0)],
+         _WF_BOUNDS + _WF_GATHER + _WF_DIRECT + 2 * 8 + 8),
+        ("ROWS unbounded..current sum", ex.rows_between(None, 0),
+         [("sum", vals, 0)],
+         _WF_BOUNDS + _WF_GATHER + _WF_SCAN + _WF_FINAL1),
+        ("ROWS -1000..+1000 max", ex.rows_between(-1000, 1000),
+         [("max", vals, 0)],
+         _WF_BOUNDS + _WF_GATHER + 2 * _WF_SCAN + _WF_FINAL2),
+    )
+    for parts in (4, 1_000_000, 100_000_000):
+        key = torch.randint(0, parts, (n,), dtype=torch.int64, device="cuda",
+                            generator=g)
+        srt = _SortCall([key], [False])
+        sb, sw = _best_of_5(srt)
+        say(f"partitions={parts:_} n={n:_}: sort best {sb*1e3:8.2f} ms  worst "
+            f"{sw*1e3:8.2f} ms")
+        win = _WindowCall(srt, 1, vals, ("sum_v",))
+        wb, ww = _best_of_5(win)
+        say(f"  otbx_window default-frame sum_v: best {wb*1e3:8.2f} ms  worst "
+            f"{ww*1e3:8.2f} ms")
+        win_sum = win.res["sum_v"].clone()
+        del win
+        torch.cuda.empty_cache()
+        for name, frame, calls, bpr in cases:
+            fc = _FrameCall(srt, 1, frame, calls)
+            fb, fw = _best_of_5(fc)
+            say(f"  {name}: otbx_window_frame best {fb*1e3:8.2f} ms  worst "
+                f"{fw*1e3:8.2f} ms (spread {(fw-fb)/fb*100:.1f} %); with the "
+                f"sort {(sb+fb)*1e3:8.2f} ms; frame / otbx_window sum_v "
+                f"{fb/wb:.2f}; {rate(bpr * n, fb)}")
+            if name == "ROWS unbounded..current sum":
+                # with no order key the default frame is the whole partition:
+                # its sum is this running sum at the partition's last row
+                say(f"    integer-valued check against otbx_window: last row "
+                    f"of the input equal: "
+                    f"{bool(fc.outs[0][0][-1] == win_sum[-1])}")
+            if name == "lag(1)":
+                def torch_lag():
+                    sk, sv = key[srt.perm], vals[srt.perm]
+                    out = torch.roll(sv, 1)
+                    first = torch.ones(n, dtype=torch.bool, device="cuda")
+                    first[1:] = sk[1:] != sk[:-1]
+                    return out, first
+                try:
+                    tb, tw = _best_of_5(torch_lag)
+                    out, first = torch_lag()
+                    ok = bool(torch.equal(first, fc.outs[0][1] != 0)) and \
+                        bool(torch.equal(out[~first], fc.outs[0][0][~first]))
+                    say(f"    plain torch (two gathers, roll, boundary mask): "
+                        f"best {tb*1e3:8.2f} ms  worst {tw*1e3:8.2f} ms; torch "
+                        f"/ frame time ratio {tb/fb:.2f}; equal: {ok}")
+                    del out, first
+                except RuntimeError as e:
+                    say(f"    plain torch composition failed: {str(e)[:120]}")
+            if name == "ROWS unbounded..current sum":
+                def torch_running():
+                    sk, sv = key[srt.perm], vals[srt.perm]
+                    cs = torch.cumsum(sv, 0)
+                    first = torch.ones(n, dtype=torch.bool, device="cuda")
+                    first[1:] = sk[1:] != sk[:-1]
+                    idx = torch.arange(n, device="cuda")
+                    start = torch.cummax(torch.where(first, idx, 0), 0)[0]
+                    return cs - (cs[start] - sv[start])
+                try:
+                    tb, tw = _best_of_5(torch_running)
+                    ok = bool(torch.equal(torch_running(), fc.outs[0][0]))
+                    say(f"    plain torch (gathers, cumsum, cummax, prefix "
+                        f"difference): best {tb*1e3:8.2f} ms  worst "
+                        f"{tw*1e3:8.2f} ms; torch / frame time ratio "
+                        f"{tb/fb:.2f}; equal (integer-valued): {ok}")
+                except RuntimeError as e:
+                    say(f"    plain torch composition failed: {str(e)[:120]}")
+            del fc
+            torch.cuda.empty_cache()
+        del srt, key, win_sum
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def bench_agg_on(keys, vals):
     """otbx_agg_i64 on given columns, best of 5 after a warm-up (seconds)"""
     n = len(keys)
@@ -1484,6 +1691,14 @@ if __name__ == "__main__":
         if "--out" in sys.argv:
             out_path = sys.argv[sys.argv.index("--out") + 1]
         bench_filter(out_path)
+        sys.exit(0)
+    if "--winframe" in sys.argv:
+        repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        out_path = os.path.join(repo, "profiles", "winframe_ops.txt")
+        if "--out" in sys.argv:
+            out_path = sys.argv[sys.argv.index("--out") + 1]
+        bench_winframe(out_path, _sizes_arg("--rows", [600_000_000])[0],
+                       _sizes_arg("--ab-rows", [200_000_000])[0])
         sys.exit(0)
     if "--groupagg" in sys.argv:
         repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
