@@ -202,6 +202,25 @@ typedef struct {
     uint64_t *dict;                /* device, uint64[3 * OTBX_Q1_DICT_MAX] */
 } otbx_q1code_desc;
 
+/* Layout of one packed Q1 price word (otbx_lineitem_dev.q1pcode; DESIGN.md
+ * §7c): a lossless 32-bit code of l_extendedprice for money columns, i.e.
+ * f64 values within a few ulp of K * 10^-e for an integer K. Two bit fields,
+ * the K field lowest (k_off == 0), each `*_bits` wide starting at bit
+ * `*_off`; a width of 0 means a single value and the field reads as 0.
+ *   K     = k_base + K field                      (fits a signed 32-bit int)
+ *   pred  = fl((double)K * mul)                   (one rounding, no fma)
+ *   delta = d_base + delta field                  (a signed ulp correction)
+ *   bits(l_extendedprice) = bits(pred) + (int64)delta   (wrapping 64-bit add)
+ * mul is the C literal 1.0, 0.1, 0.01, 0.001 or 0.0001 for scale_exp
+ * 0..4. k_base + K field and d_base + delta field never leave int32.
+ * sizeof == 40. */
+typedef struct {
+    int32_t scale_exp;             /* e: K = llrint(x * 10^e), 0..4 */
+    double mul;                    /* the literal 10^-e */
+    int32_t k_base, k_off, k_bits;
+    int32_t d_base, d_off, d_bits; /* d_bits <= 8 */
+} otbx_q1price_desc;
+
 typedef struct {
     int64_t n;
     int64_t *l_orderkey;      /* may be NULL if not staged (Q1 needs none) */
@@ -230,6 +249,14 @@ typedef struct {
      * columns. q1desc is meaningful only while q1code is non-NULL. */
     uint32_t *q1code;
     otbx_q1code_desc q1desc;
+    /* optional packed Q1 price column (otbx_build_q1pcodes, built once at
+     * staging after q1code): one 32-bit word per row from which
+     * l_extendedprice is rebuilt bit for bit, laid out as q1pdesc says. Q1
+     * then streams q1code + q1pcode, 8 B/row instead of 12. NULL = Q1 reads
+     * l_extendedprice. Only used together with q1code; q1pdesc is meaningful
+     * only while q1pcode is non-NULL. */
+    uint32_t *q1pcode;
+    otbx_q1price_desc q1pdesc;
 } otbx_lineitem_dev;
 
 typedef struct {
@@ -297,6 +324,36 @@ otbx_status otbx_build_q1codes(const otbx_lineitem_dev *t,
                                uint32_t *codes_dev, uint64_t *dict_dev,
                                otbx_q1code_desc *desc_host, int32_t *ok_host,
                                void *stream);
+/* Plan the packed Q1 price word. Pure host code (no HIP call). Inputs, one
+ * entry per candidate exponent e = 0..4 (scale 10^e): bad[e] != 0 when some
+ * x * 10^e was not finite or K = llrint(x * 10^e) left int32; otherwise the
+ * column's min/max of K and of delta = bits(x) - bits(fl((double)K * 10^-e)).
+ * k_bits = bits(kmax - kmin), d_bits = bits(dmax - dmin), both differences
+ * formed in 64 bit. A candidate fits when it is not bad, d_bits <= 8,
+ * k_bits + d_bits <= 32 and dmin, dmax lie in int32 (d_base is one). The
+ * fitting candidate with the fewest total bits wins, ties go to the smaller
+ * e. *fits_host = 1 and *desc filled (K field at offset 0, delta field above
+ * it) when one fits; otherwise *fits_host = 0 and *desc is untouched.
+ * OTBX_ERR_INVALID only for NULL pointers. */
+otbx_status otbx_q1price_plan(const int32_t *bad, const int64_t *kmin,
+                              const int64_t *kmax, const int64_t *dmin,
+                              const int64_t *dmax, otbx_q1price_desc *desc,
+                              int32_t *fits_host);
+/* Build the packed Q1 price column of a staged lineitem table. One pass
+ * over l_extendedprice collects the five candidates' statistics on the
+ * device, otbx_q1price_plan picks the layout, a second pass writes one word
+ * per row to pcodes_dev (uint32[t->n]), decodes the word it wrote with the
+ * Q1 kernel's own decode and compares it bit for bit with the source double.
+ * *ok_host = 1 and *desc_host filled on success; the caller then sets
+ * t->q1pcode / t->q1pdesc. *ok_host = 0 (caller leaves q1pcode NULL, Q1
+ * keeps streaming l_extendedprice) when t->q1code is NULL, t->n == 0,
+ * l_extendedprice is not staged, no candidate fits (NaN, +-Inf, -0.0 among
+ * positive values, doubles without decimal structure) or the round trip
+ * failed. Synchronous (staging-time only), like otbx_build_q1codes. */
+otbx_status otbx_build_q1pcodes(const otbx_lineitem_dev *t,
+                                uint32_t *pcodes_dev,
+                                otbx_q1price_desc *desc_host,
+                                int32_t *ok_host, void *stream);
 /* build the q9rec cache from the staged columns (32 B/row into recs_dev) */
 otbx_status otbx_build_q9recs(const otbx_lineitem_dev *l, void *recs_dev,
                               void *stream);
@@ -335,9 +392,13 @@ otbx_status otbx_q1_partial(const otbx_lineitem_dev *t, int32_t cutoff_day,
  * 2 = 4 rows/lane + non-temporal loads (all three read the raw columns,
  * 38 B/row); 3 = the packed code column + l_extendedprice, 12 B/row, 4
  * rows/lane; 4 = as 3 with 8 rows/lane; 5 = as 3, accumulating only the
- * group slots in q1desc.gid_present. Variants 3 to 5 need t->q1code and
- * return OTBX_ERR_INVALID without launching anything when it is NULL.
- * otbx_q1_partial dispatches variant 5 when t->q1code is set, else 2. */
+ * group slots in q1desc.gid_present; 6 = as 5 with the price decoded from
+ * the packed price column q1pcode instead of l_extendedprice, 8 B/row;
+ * 7 = as 6 with 8 rows/lane. Variants 3 to 7 need t->q1code, 6 and 7 also
+ * t->q1pcode and a valid q1pdesc; they return OTBX_ERR_INVALID without
+ * launching anything otherwise, as does any variant above 7.
+ * otbx_q1_partial dispatches variant 7 when t->q1pcode is set, else 5 when
+ * t->q1code is set, else 2. */
 otbx_status otbx_q1_partial_variant(const otbx_lineitem_dev *t,
                                     int32_t cutoff_day, double *sums_dev,
                                     int64_t *counts_dev, void *stream,

@@ -44,6 +44,17 @@ class Q1CodeDesc(C.Structure):
     ]
 
 
+class Q1PriceDesc(C.Structure):
+    """otbx_q1price_desc (include/otbx.h): layout of the packed Q1 price
+    word, 40 bytes."""
+    _fields_ = [
+        ("scale_exp", C.c_int32),
+        ("mul", C.c_double),
+        ("k_base", C.c_int32), ("k_off", C.c_int32), ("k_bits", C.c_int32),
+        ("d_base", C.c_int32), ("d_off", C.c_int32), ("d_bits", C.c_int32),
+    ]
+
+
 class LineitemDev(C.Structure):
     _fields_ = [
         ("n", C.c_int64),
@@ -58,6 +69,8 @@ class LineitemDev(C.Structure):
         ("l_partkey32", C.c_void_p),
         ("q1code", C.c_void_p),
         ("q1desc", Q1CodeDesc),
+        ("q1pcode", C.c_void_p),
+        ("q1pdesc", Q1PriceDesc),
     ]
 
 
@@ -268,6 +281,9 @@ def lib():
         _lib.otbx_q1code_plan.argtypes = [
             C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
             C.POINTER(Q1CodeDesc), C.POINTER(C.c_int32)]
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        _lib.otbx_q1price_plan.argtypes = [
+            i32p, i64p, i64p, i64p, i64p, C.POINTER(Q1PriceDesc), i32p]
     return _lib
 
 
@@ -288,6 +304,7 @@ EXPORTED_SYMBOLS = [
     "otbx_gen_part_dev", "otbx_q9_workspace_bytes", "otbx_q9_partial",
     "otbx_stage_pages", "otbx_build_q9recs", "otbx_build_key32",
     "otbx_build_q1codes", "otbx_q1code_plan",
+    "otbx_build_q1pcodes", "otbx_q1price_plan",
     "otbx_scan_count", "otbx_q1_partial", "otbx_q1_partial_variant",
     "otbx_q3_workspace_bytes", "otbx_q3_partial", "otbx_filter_customer",
     "otbx_topk_by_revenue",

@@ -324,7 +324,9 @@ extern "C" otbx_status otbx_scan_count(const int32_t *sd, int64_t n,
  * algorithmic; variants 0-2, the path for tables without a code column),
  * k_q1_coded reads the staged packed code column plus l_extendedprice
  * (12 B/row; variants 3-5, DESIGN.md §7b, the default when
- * otbx_build_q1codes succeeded). The 6-combo group domain lives in
+ * otbx_build_q1codes succeeded) or plus the packed price column (8 B/row;
+ * variants 6-7, DESIGN.md §7c, the default when otbx_build_q1pcodes
+ * succeeded too). The 6-combo group domain lives in
  * per-lane registers (compile-time-indexed — runtime indexing would go to
  * scratch), selected by compare+fma; wave64 shuffle reduction, per-block LDS
  * combine, one device atomic per (group,agg) per block.
@@ -654,16 +656,50 @@ __device__ __forceinline__ void d_q1c_row(double (&acc)[NG][Q1_NS],
     }
 }
 
-/* R: rows per lane per iteration (4 or 8); NG: group slots accumulated */
-template <int R, int NG>
+/* variants 6 / 7: the packed price word (otbx.h q1pcode)
+ * replaces l_extendedprice, 8 B/row instead of 12. By-value kernarg; the K
+ * field is the lowest of the word, so it is taken with a mask (a 32-bit
+ * wide field is outside v_bfe_u32's 5-bit width operand). */
+struct q1p_fields {
+    uint32_t k_mask;
+    int32_t k_base;
+    uint32_t d_off, d_bits;
+    int32_t d_base;
+    double mul;
+};
+
+/* the one decode of a price word: the encode pass checks every word with
+ * it, the Q1 kernel reads prices through it. (double)K and K * mul are one
+ * v_cvt_f64_i32 and one v_mul_f64 (no contraction: -ffp-contract=off), so
+ * pred is the same double wherever it is computed. */
+__device__ __forceinline__ double d_q1p_decode(uint32_t w, const q1p_fields &p)
+{
+    int32_t k = (int32_t)((uint32_t)p.k_base + (w & p.k_mask));
+    double pred = (double)k * p.mul;
+    int32_t d = p.d_base + (int32_t)__builtin_amdgcn_ubfe(w, p.d_off, p.d_bits);
+    return __longlong_as_double((long long)(
+        (unsigned long long)__double_as_longlong(pred) +
+        (unsigned long long)(long long)d));
+}
+
+/* R: rows per lane per iteration (4 or 8); NG: group slots accumulated;
+ * PC: `price` is the packed price column (uint32 words decoded through pf)
+ * instead of l_extendedprice (f64). With PC and R = 4 (variant 6) every lane
+ * sees the same rows in the same order as variant 5 and every operand is
+ * bit-identical (the decode is lossless), so per-lane, per-wave and
+ * per-block partials are bit-identical to variant 5's; only the order of
+ * the block atomics differs. */
+template <int R, int NG, bool PC>
 __launch_bounds__(256, 2)
 __global__ void k_q1_coded(const uint32_t *__restrict__ code,
-                           const double *__restrict__ price,
+                           const void *__restrict__ price_col,
                            const uint64_t *__restrict__ dict,
-                           const q1c_fields f, int64_t n, int32_t cut_rel,
-                           double *__restrict__ out_sums,
+                           const q1c_fields f, const q1p_fields pf, int64_t n,
+                           int32_t cut_rel, double *__restrict__ out_sums,
                            unsigned long long *__restrict__ out_counts)
 {
+    const double *price = (const double *)price_col;
+    const uint32_t *pcode = (const uint32_t *)price_col;
     __shared__ double sdict[3 * OTBX_Q1_DICT_MAX];   /* 6 KB */
     for (int i = threadIdx.x; i < 3 * OTBX_Q1_DICT_MAX; i += 256)
         sdict[i] = __longlong_as_double((long long)dict[i]);
@@ -682,6 +718,7 @@ __global__ void k_q1_coded(const uint32_t *__restrict__ code,
     int64_t nq = n / R;
     const v4i *code4 = (const v4i *)code;
     const double2 *price2 = (const double2 *)price;
+    const v4i *pcode4 = (const v4i *)pcode;
     for (int64_t i = tid; i < nq; i += stride) {
         uint32_t cw[R];
         double pv[R];
@@ -693,11 +730,25 @@ __global__ void k_q1_coded(const uint32_t *__restrict__ code,
             cw[4 * k + 2] = (uint32_t)c.z;
             cw[4 * k + 3] = (uint32_t)c.w;
         }
+        if (PC) {
+            uint32_t pw[R];
 #pragma unroll
-        for (int k = 0; k < R / 2; k++) {
-            double2 p = ld2<true>(&price2[(R / 2) * i + k]);
-            pv[2 * k] = p.x;
-            pv[2 * k + 1] = p.y;
+            for (int k = 0; k < R / 4; k++) {
+                v4i c = __builtin_nontemporal_load(&pcode4[(R / 4) * i + k]);
+                pw[4 * k] = (uint32_t)c.x;
+                pw[4 * k + 1] = (uint32_t)c.y;
+                pw[4 * k + 2] = (uint32_t)c.z;
+                pw[4 * k + 3] = (uint32_t)c.w;
+            }
+#pragma unroll
+            for (int j = 0; j < R; j++) pv[j] = d_q1p_decode(pw[j], pf);
+        } else {
+#pragma unroll
+            for (int k = 0; k < R / 2; k++) {
+                double2 p = ld2<true>(&price2[(R / 2) * i + k]);
+                pv[2 * k] = p.x;
+                pv[2 * k + 1] = p.y;
+            }
         }
 #pragma unroll
         for (int j = 0; j < R; j++)
@@ -706,7 +757,9 @@ __global__ void k_q1_coded(const uint32_t *__restrict__ code,
     /* tail rows (n % R) by thread 0 of block 0 */
     if (blockIdx.x == 0 && threadIdx.x == 0)
         for (int64_t i = nq * R; i < n; i++)
-            d_q1c_row<NG>(acc, cnt, code[i], price[i], sdict, f, cut_rel);
+            d_q1c_row<NG>(acc, cnt, code[i],
+                          PC ? d_q1p_decode(pcode[i], pf) : price[i], sdict,
+                          f, cut_rel);
     /* reduction, LDS combine and atomics as in k_q1_partial_v2; group g
      * lands in output slot f.slot[g] */
 #pragma unroll
@@ -763,6 +816,30 @@ static bool q1c_desc_ok(const otbx_q1code_desc *d)
            d->qty_bits <= 8 && d->disc_bits <= 8 && d->tax_bits <= 8;
 }
 
+static const double q1p_mul[5] = {1.0, 0.1, 0.01, 0.001, 0.0001};
+static const double q1p_scale[5] = {1.0, 10.0, 100.0, 1000.0, 10000.0};
+
+/* a price descriptor the coded kernel can decode with: the K field lowest,
+ * both fields inside the word, the correction at most 8 bits, and mul the
+ * literal of its exponent */
+static bool q1p_desc_ok(const otbx_q1price_desc *d)
+{
+    if (d->k_off != 0 || d->k_bits < 0 || d->k_bits > 32 || d->d_off < 0 ||
+        d->d_bits < 0 || d->d_bits > 8 || d->d_off + d->d_bits > 32 ||
+        d->d_off < d->k_bits)
+        return false;
+    return d->scale_exp >= 0 && d->scale_exp <= 4 &&
+           d->mul == q1p_mul[d->scale_exp];
+}
+
+static q1p_fields q1p_fields_of(const otbx_q1price_desc *d)
+{
+    q1p_fields p = {d->k_bits >= 32 ? 0xffffffffu : (1u << d->k_bits) - 1u,
+                    d->k_base, (uint32_t)d->d_off, (uint32_t)d->d_bits,
+                    d->d_base, d->mul};
+    return p;
+}
+
 extern "C" otbx_status otbx_q1_partial_variant(const otbx_lineitem_dev *t,
                                                int32_t cutoff_day,
                                                double *sums_dev,
@@ -771,8 +848,10 @@ extern "C" otbx_status otbx_q1_partial_variant(const otbx_lineitem_dev *t,
                                                int variant)
 {
     if (!t || !sums_dev || !counts_dev) return OTBX_ERR_INVALID;
-    if (variant >= 3 && (variant > 5 || !t->q1code || !t->l_extendedprice ||
-                         !q1c_desc_ok(&t->q1desc)))
+    if (variant >= 3 && (variant > 7 || !t->q1code || !q1c_desc_ok(&t->q1desc)))
+        return OTBX_ERR_INVALID;
+    if (variant >= 6 ? !t->q1pcode || !q1p_desc_ok(&t->q1pdesc)
+                     : variant >= 3 && !t->l_extendedprice)
         return OTBX_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     HIP_CHECK(hipMemsetAsync(sums_dev, 0, Q1_NG * Q1_NS * sizeof(double), s));
@@ -807,29 +886,43 @@ extern "C" otbx_status otbx_q1_partial_variant(const otbx_lineitem_dev *t,
         int64_t rel = (int64_t)cutoff_day - (int64_t)d->date_base;
         int32_t cut_rel = rel < 0 ? -1 : rel > INT32_MAX ? INT32_MAX
                                                          : (int32_t)rel;
-#define Q1C_LAUNCH(R, NG)                                                   \
-    hipLaunchKernelGGL((k_q1_coded<R, NG>), dim3(grid_for(t->n / R, 256)),  \
-                       dim3(256), 0, s, t->q1code, t->l_extendedprice,      \
-                       d->dict, f, t->n, cut_rel, sums_dev,                 \
+        const bool pc = variant >= 6;
+        q1p_fields pf = {};
+        if (pc) pf = q1p_fields_of(&t->q1pdesc);
+#define Q1C_LAUNCH(R, NG, PC)                                               \
+    hipLaunchKernelGGL((k_q1_coded<R, NG, PC>),                             \
+                       dim3(grid_for(t->n / R, 256)), dim3(256), 0, s,      \
+                       t->q1code,                                           \
+                       PC ? (const void *)t->q1pcode                        \
+                          : (const void *)t->l_extendedprice,               \
+                       d->dict, f, pf, t->n, cut_rel, sums_dev,             \
                        (unsigned long long *)counts_dev)
+#define Q1C_LAUNCH_NG(R, PC)                                                \
+    switch (ng) {                                                           \
+    case 1: Q1C_LAUNCH(R, 1, PC); break;                                    \
+    case 2: Q1C_LAUNCH(R, 2, PC); break;                                    \
+    case 3: Q1C_LAUNCH(R, 3, PC); break;                                    \
+    case 4: Q1C_LAUNCH(R, 4, PC); break;                                    \
+    case 5: Q1C_LAUNCH(R, 5, PC); break;                                    \
+    default: Q1C_LAUNCH(R, 6, PC); break;                                   \
+    }
         if (variant == 3)
-            Q1C_LAUNCH(4, 6);
+            Q1C_LAUNCH(4, 6, false);
         else if (variant == 4)
-            Q1C_LAUNCH(8, 6);
+            Q1C_LAUNCH(8, 6, false);
         else {
             /* only the slots present in the table (real Q1 data: 4 of 6) */
             int ng = 0;
             for (uint32_t g = 0; g < Q1_NG; g++)
                 if (d->gid_present >> g & 1) f.slot[ng++] = g;
-            switch (ng) {
-            case 1: Q1C_LAUNCH(4, 1); break;
-            case 2: Q1C_LAUNCH(4, 2); break;
-            case 3: Q1C_LAUNCH(4, 3); break;
-            case 4: Q1C_LAUNCH(4, 4); break;
-            case 5: Q1C_LAUNCH(4, 5); break;
-            default: Q1C_LAUNCH(4, 6); break;
-            }
+            if (variant == 5)
+                Q1C_LAUNCH_NG(4, false)
+            else if (variant == 6)
+                Q1C_LAUNCH_NG(4, true)
+            else
+                Q1C_LAUNCH_NG(8, true)
         }
+#undef Q1C_LAUNCH_NG
 #undef Q1C_LAUNCH
     } else
         hipLaunchKernelGGL(k_q1_partial_v2<true>, dim3(grid_for(t->n / 4, 256)),
@@ -853,7 +946,12 @@ extern "C" otbx_status otbx_q1_partial(const otbx_lineitem_dev *t,
                                        int64_t *counts_dev, void *stream,
                                        float *kernel_ms)
 {
-    /* With the staged code column (otbx_build_q1codes) the scan reads 12
+    /* With the packed price column as well (otbx_build_q1pcodes) the scan
+     * reads 8 B/row; of the two kernels that decode it variant 7 (8 rows per
+     * lane) had the lower time in each of 8 interleaved rounds at SF100:
+     * median 1.080 ms vs 1.128 (v6, 4 rows/lane) and 1.285 (v5) in the same
+     * process (profiles/q1_price_ab.txt).
+     * With the staged code column alone (otbx_build_q1codes) the scan reads 12
      * B/row; of the coded kernels variant 5 (only the group slots present in
      * the table) measured best at SF100: 1.26 ms vs 1.36 (v3) and 1.88 (v4,
      * 8 rows/lane), against 3.78 ms for variant 2 in the same process — 8
@@ -863,7 +961,8 @@ extern "C" otbx_status otbx_q1_partial(const otbx_lineitem_dev *t,
      * interleaved A/B, 8 rounds (profiles/r01_q1_ab.txt) */
     if (!t) return OTBX_ERR_INVALID;
     return otbx_q1_partial_variant(t, cutoff_day, sums_dev, counts_dev, stream,
-                                   kernel_ms, t->q1code ? 5 : 2);
+                                   kernel_ms,
+                                   t->q1code ? (t->q1pcode ? 7 : 5) : 2);
 }
 
 /* ---- staging: build the packed Q1 code column (otbx.h q1code) ---- */
@@ -1151,6 +1250,231 @@ extern "C" otbx_status otbx_build_q1codes(const otbx_lineitem_dev *t,
     HIP_CHECK(hipStreamSynchronize(s));
     if (h_st->flags) return OTBX_OK;
     d.gid_present = (int32_t)h_st->present;
+    *desc_host = d;
+    *ok_host = 1;
+    return OTBX_OK;
+}
+
+/* ---- staging: build the packed Q1 price column (otbx.h q1pcode) ---- */
+
+#define Q1P_NE 5   /* candidate exponents e = 0..4 */
+
+struct q1p_state {   /* device scratch + its pinned host mirror */
+    long long dmin[Q1P_NE], dmax[Q1P_NE];
+    int kmin[Q1P_NE], kmax[Q1P_NE];
+    unsigned int bad[Q1P_NE];
+    unsigned int mismatch;   /* encode round trip failed */
+};
+
+/* pass 1: per candidate exponent, whether every K = llrint(x * 10^e) is a
+ * signed 32-bit integer, and the ranges of K and of the ulp correction
+ * delta = bits(x) - bits(fl((double)K * 10^-e)). Lanes reduce per wave, waves
+ * per block in LDS, one set of device atomics per block. */
+__global__ void k_q1p_collect(const double *__restrict__ price, int64_t n,
+                              q1p_state *st)
+{
+    const double scale[Q1P_NE] = {1.0, 10.0, 100.0, 1000.0, 10000.0};
+    const double mul[Q1P_NE] = {1.0, 0.1, 0.01, 0.001, 0.0001};
+    __shared__ q1p_state ls;
+    if (threadIdx.x < Q1P_NE) {
+        ls.dmin[threadIdx.x] = LLONG_MAX;
+        ls.dmax[threadIdx.x] = LLONG_MIN;
+        ls.kmin[threadIdx.x] = INT_MAX;
+        ls.kmax[threadIdx.x] = INT_MIN;
+        ls.bad[threadIdx.x] = 0;
+    }
+    __syncthreads();
+    long long dmin[Q1P_NE], dmax[Q1P_NE];
+    int kmin[Q1P_NE], kmax[Q1P_NE];
+    unsigned int bad[Q1P_NE];
+#pragma unroll
+    for (int e = 0; e < Q1P_NE; e++) {
+        dmin[e] = LLONG_MAX;
+        dmax[e] = LLONG_MIN;
+        kmin[e] = INT_MAX;
+        kmax[e] = INT_MIN;
+        bad[e] = 0;
+    }
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        double x = price[i];
+        unsigned long long xb = (unsigned long long)__double_as_longlong(x);
+#pragma unroll
+        for (int e = 0; e < Q1P_NE; e++) {
+            double y = x * scale[e];
+            /* NaN fails the comparison; llrint may still round up to 2^31 */
+            long long k = fabs(y) < 2147483648.0 ? llrint(y) : LLONG_MAX;
+            if (k > INT_MAX) {
+                bad[e] = 1;
+                continue;
+            }
+            double pred = (double)(int)k * mul[e];
+            long long d = (long long)(
+                xb - (unsigned long long)__double_as_longlong(pred));
+            kmin[e] = (int)k < kmin[e] ? (int)k : kmin[e];
+            kmax[e] = (int)k > kmax[e] ? (int)k : kmax[e];
+            dmin[e] = d < dmin[e] ? d : dmin[e];
+            dmax[e] = d > dmax[e] ? d : dmax[e];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < Q1P_NE; e++) {
+        for (int off = WAVE / 2; off > 0; off >>= 1) {
+            int a = __shfl_down(kmin[e], off, WAVE);
+            int b = __shfl_down(kmax[e], off, WAVE);
+            long long c = __shfl_down(dmin[e], off, WAVE);
+            long long d = __shfl_down(dmax[e], off, WAVE);
+            kmin[e] = a < kmin[e] ? a : kmin[e];
+            kmax[e] = b > kmax[e] ? b : kmax[e];
+            dmin[e] = c < dmin[e] ? c : dmin[e];
+            dmax[e] = d > dmax[e] ? d : dmax[e];
+            bad[e] |= __shfl_down(bad[e], off, WAVE);
+        }
+        if ((threadIdx.x % WAVE) == 0) {
+            atomicMin(&ls.kmin[e], kmin[e]);
+            atomicMax(&ls.kmax[e], kmax[e]);
+            atomicMin(&ls.dmin[e], dmin[e]);
+            atomicMax(&ls.dmax[e], dmax[e]);
+            if (bad[e]) atomicOr(&ls.bad[e], 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < Q1P_NE) {
+        int e = threadIdx.x;
+        atomicMin(&st->kmin[e], ls.kmin[e]);
+        atomicMax(&st->kmax[e], ls.kmax[e]);
+        atomicMin(&st->dmin[e], ls.dmin[e]);
+        atomicMax(&st->dmax[e], ls.dmax[e]);
+        if (ls.bad[e]) atomicOr(&st->bad[e], 1u);
+    }
+}
+
+/* pass 2: one price word per row, then decode that word with the Q1
+ * kernel's own d_q1p_decode and compare it bit-for-bit with the source
+ * double (k_q1c_encode's rule: the build checks its own round trip). */
+__global__ void k_q1p_encode(const double *__restrict__ price, int64_t n,
+                             const otbx_q1price_desc d, const q1p_fields pf,
+                             double scale, uint32_t *__restrict__ pcodes,
+                             q1p_state *st)
+{
+    unsigned int bad = 0;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        double x = price[i];
+        unsigned long long xb = (unsigned long long)__double_as_longlong(x);
+        double y = x * scale;
+        long long k = fabs(y) < 2147483648.0 ? llrint(y) : LLONG_MAX;
+        bad |= k > INT_MAX;
+        double pred = (double)(int)k * d.mul;
+        unsigned long long delta =
+            xb - (unsigned long long)__double_as_longlong(pred);
+        uint64_t kf = (uint64_t)k - (uint64_t)(long long)d.k_base;
+        uint64_t df = delta - (unsigned long long)(long long)d.d_base;
+        bad |= (kf >> 32) != 0 || (df >> 8) != 0;
+        uint64_t w = (kf & 0xffffffffull) << d.k_off | (df & 0xffull) << d.d_off;
+        uint32_t word = (uint32_t)w;
+        bad |= (w >> 32) != 0;
+        bad |= (unsigned long long)__double_as_longlong(
+                   d_q1p_decode(word, pf)) != xb;
+        pcodes[i] = word;
+    }
+    if (bad) atomicOr(&st->mismatch, 1u);
+}
+
+extern "C" otbx_status otbx_q1price_plan(const int32_t *bad,
+                                         const int64_t *kmin,
+                                         const int64_t *kmax,
+                                         const int64_t *dmin,
+                                         const int64_t *dmax,
+                                         otbx_q1price_desc *desc,
+                                         int32_t *fits_host)
+{
+    if (!bad || !kmin || !kmax || !dmin || !dmax || !desc || !fits_host)
+        return OTBX_ERR_INVALID;
+    *fits_host = 0;
+    int best = -1, best_k = 0, best_d = 0;
+    for (int e = 0; e < Q1P_NE; e++) {
+        if (bad[e] || kmin[e] > kmax[e] || dmin[e] > dmax[e] ||
+            kmin[e] < INT32_MIN || kmax[e] > INT32_MAX ||
+            dmin[e] < INT32_MIN || dmax[e] > INT32_MAX)
+            continue;
+        int32_t kb = q1c_bits_of((uint64_t)kmax[e] - (uint64_t)kmin[e]);
+        int32_t db = q1c_bits_of((uint64_t)dmax[e] - (uint64_t)dmin[e]);
+        if (db > 8 || kb + db > 32) continue;
+        if (best < 0 || kb + db < best_k + best_d) {
+            best = e;
+            best_k = kb;
+            best_d = db;
+        }
+    }
+    if (best < 0) return OTBX_OK;
+    desc->scale_exp = best;
+    desc->mul = q1p_mul[best];
+    desc->k_base = (int32_t)kmin[best];
+    desc->k_off = 0;
+    desc->k_bits = best_k;
+    desc->d_base = (int32_t)dmin[best];
+    desc->d_off = best_k;
+    desc->d_bits = best_d;
+    *fits_host = 1;
+    return OTBX_OK;
+}
+
+extern "C" otbx_status otbx_build_q1pcodes(const otbx_lineitem_dev *t,
+                                           uint32_t *pcodes_dev,
+                                           otbx_q1price_desc *desc_host,
+                                           int32_t *ok_host, void *stream)
+{
+    if (!t || !desc_host || !ok_host) return OTBX_ERR_INVALID;
+    *ok_host = 0;
+    if (t->n <= 0 || !t->q1code || !t->l_extendedprice)
+        return OTBX_OK;   /* nothing to build: Q1 keeps l_extendedprice */
+    if (!pcodes_dev) return OTBX_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    static q1p_state *d_st = nullptr;
+    static q1p_state *h_st = nullptr;
+    if (!d_st) SCR_ALLOC_DEV(d_st, sizeof(q1p_state));
+    if (!h_st) SCR_ALLOC_HOST(h_st, sizeof(q1p_state));
+    for (int e = 0; e < Q1P_NE; e++) {
+        h_st->dmin[e] = LLONG_MAX;
+        h_st->dmax[e] = LLONG_MIN;
+        h_st->kmin[e] = INT_MAX;
+        h_st->kmax[e] = INT_MIN;
+        h_st->bad[e] = 0;
+    }
+    h_st->mismatch = 0;
+    HIP_CHECK(hipMemcpyAsync(d_st, h_st, sizeof(q1p_state),
+                             hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_q1p_collect, dim3(grid_for(t->n, 256)), dim3(256), 0,
+                       s, t->l_extendedprice, t->n, d_st);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h_st, d_st, sizeof(q1p_state),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+
+    int32_t bad[Q1P_NE], fits = 0;
+    int64_t kmin[Q1P_NE], kmax[Q1P_NE], dmin[Q1P_NE], dmax[Q1P_NE];
+    for (int e = 0; e < Q1P_NE; e++) {
+        bad[e] = (int32_t)h_st->bad[e];
+        kmin[e] = h_st->kmin[e];
+        kmax[e] = h_st->kmax[e];
+        dmin[e] = h_st->dmin[e];
+        dmax[e] = h_st->dmax[e];
+    }
+    otbx_q1price_desc d;
+    memset(&d, 0, sizeof(d));
+    otbx_q1price_plan(bad, kmin, kmax, dmin, dmax, &d, &fits);
+    if (!fits || !q1p_desc_ok(&d)) return OTBX_OK;
+    hipLaunchKernelGGL(k_q1p_encode, dim3(grid_for(t->n, 256)), dim3(256), 0,
+                       s, t->l_extendedprice, t->n, d, q1p_fields_of(&d),
+                       q1p_scale[d.scale_exp], pcodes_dev, d_st);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(&h_st->mismatch, &d_st->mismatch,
+                             sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (h_st->mismatch) return OTBX_OK;
     *desc_host = d;
     *ok_host = 1;
     return OTBX_OK;

@@ -21,9 +21,9 @@ from ._lib import (AGG_FUNCS, FB_CURRENT, FB_OFFSET, FB_UNBOUNDED,
                    MAX_TEXT_RANK_COLS, MAX_WINCALLS, TEXT_ENCODINGS, TXT_OPS,
                    WIN_FUNCS, AggCallsDev, CustomerDev, ExprDev, FrameDev,
                    KeysetDev, LineitemDev, OrdersDev, OtbxError, PartDev,
-                   Q1_DICT_MAX, Q1CodeDesc, QualDev, SortSpecDev, TextColDev,
-                   TextPredDev, TextSetDev, WinCallDev, WindowOutDev, call,
-                   check, lib)
+                   Q1_DICT_MAX, Q1CodeDesc, Q1PriceDesc, QualDev, SortSpecDev,
+                   TextColDev, TextPredDev, TextSetDev, WinCallDev,
+                   WindowOutDev, call, check, lib)
 
 Q1_SLOT_ORDER = [(b"A", b"F"), (b"A", b"O"), (b"N", b"F"),
                  (b"N", b"O"), (b"R", b"F"), (b"R", b"O")]
@@ -168,8 +168,10 @@ class GpuLineitem:
     def _stage_q1codes(self):
         """Build the packed Q1 code column (otbx_build_q1codes). The struct
         fields are set only when the build reports success; otherwise
-        q1code stays NULL and otbx_q1_partial reads the raw columns."""
-        self._q1code = self._q1dict = None
+        q1code stays NULL and otbx_q1_partial reads the raw columns. After a
+        successful build the packed price column (otbx_build_q1pcodes)
+        follows by the same rule."""
+        self._q1code = self._q1dict = self._q1pcode = None
         if self.n == 0 or any(self.t.get(c) is None for c in self.Q1_COLS):
             return
         codes = torch.empty(self.n, dtype=torch.int32, device="cuda")
@@ -184,11 +186,25 @@ class GpuLineitem:
         self._q1code, self._q1dict = codes, qdict   # keep the tensors alive
         self.cstruct.q1desc = desc
         self.cstruct.q1code = C.c_void_p(codes.data_ptr())
+        # the packed price column (otbx.h q1pcode) is only used next to the
+        # code column: 8 B/row instead of 12 when l_extendedprice is money
+        pcodes = torch.empty(self.n, dtype=torch.int32, device="cuda")
+        pdesc = Q1PriceDesc()
+        ok = C.c_int32(0)
+        call("otbx_build_q1pcodes", C.byref(self.cstruct),
+             C.c_void_p(pcodes.data_ptr()), C.byref(pdesc), C.byref(ok),
+             _stream())
+        if not ok.value:
+            return
+        self._q1pcode = pcodes
+        self.cstruct.q1pdesc = pdesc
+        self.cstruct.q1pcode = C.c_void_p(pcodes.data_ptr())
 
     def bytes_staged(self):
         """HBM held by the table: the columns plus every derived cache."""
         caches = [getattr(self, a, None) for a in
-                  ("_q9rec", "_okey32", "_pkey32", "_q1code", "_q1dict")]
+                  ("_q9rec", "_okey32", "_pkey32", "_q1code", "_q1dict",
+                   "_q1pcode")]
         return sum(v.numel() * v.element_size()
                    for v in list(self.t.values()) + caches if v is not None)
 

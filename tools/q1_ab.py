@@ -2,10 +2,11 @@
 """Within-probe interleaved A/B of the Q1 kernel variants (guide §5.4 rule 24):
 N rounds × variants interleaved in one process; reports median/min ms and
 checks result parity across variants. Variants 0-2 read the raw columns
-(38 B/row), 3 to 5 the staged code column + l_extendedprice (12 B/row); the
-bandwidth printed is each variant's own physical bytes over its time.
+(38 B/row), 3 to 5 the staged code column + l_extendedprice (12 B/row), 6 and
+7 the code column + the packed price column (8 B/row); the bandwidth printed
+is each variant's own physical bytes over its time.
 
-usage: q1_ab.py [SF [ROUNDS [VARIANT ...]]]   (default 100, 8, all six)"""
+usage: q1_ab.py [SF [ROUNDS [VARIANT ...]]]   (default 100, 8, all eight)"""
 import ctypes as C
 import statistics
 import sys
@@ -20,7 +21,7 @@ from opentenbase_amd._lib import call  # noqa: E402
 def main():
     sf = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-    variants = [int(v) for v in sys.argv[3:]] or [0, 1, 2, 3, 4, 5]
+    variants = [int(v) for v in sys.argv[3:]] or [0, 1, 2, 3, 4, 5, 6, 7]
     ex.init_device(0)
     li = ex.GpuLineitem.generate(sf * 6_000_000, with_orderkey=False)
     torch.cuda.synchronize()
@@ -49,7 +50,7 @@ def main():
         for v in variants:
             times[v].append(run(v)[0])
     for v in variants:
-        bytes_ = li.n * (38 if v < 3 else 12)
+        bytes_ = li.n * (38 if v < 3 else 12 if v < 6 else 8)
         med = statistics.median(times[v])
         mn = min(times[v])
         print(f"variant {v}: median {med:.3f} ms  min {mn:.3f} ms  "
