@@ -35,6 +35,22 @@ static inline int grid_for(int64_t work, int block)
 
 static inline size_t align256_sz(size_t x) { return (x + 255) & ~(size_t)255; }
 
+/* clang vector types: what __builtin_nontemporal_load takes for a 16-B load */
+typedef double v2d __attribute__((ext_vector_type(2)));
+typedef long long v2l __attribute__((ext_vector_type(2)));
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+/* The one registry of lazily allocated per-process scratch (defined in
+ * otbx.hip next to otbx_finish, which releases every registered slot and
+ * nulls the static that owns it). Not part of the C-ABI. */
+__attribute__((visibility("hidden")))
+hipError_t otbx_scr_alloc(void **slot, size_t bytes, int host);
+
+#define SCR_ALLOC_DEV(p, bytes) \
+    HIP_CHECK(otbx_scr_alloc((void **)&(p), (bytes), 0))
+#define SCR_ALLOC_HOST(p, bytes) \
+    HIP_CHECK(otbx_scr_alloc((void **)&(p), (bytes), 1))
+
 /* blockDim.x for device functions. The HIP header's form picks between the
  * group size and the last group's remainder; written in a kernel it folds
  * to one scalar load (work-groups are uniform), inside an inlined helper it

@@ -415,7 +415,7 @@ class GpuQ1PartialAgg(CustomScanState):
     def explain(self):
         if self.kernel_ms is None:
             return None
-        return {"k_q1_partial (SeqScan+Qual+Project+PartialAgg, fused)":
+        return {"otbx_q1_partial (SeqScan+Qual+Project+PartialAgg, fused)":
                 self.kernel_ms}
 
 

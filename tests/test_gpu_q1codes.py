@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from q1_ref import gid_of, host_cols, ref_q1_partial
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
@@ -61,11 +63,6 @@ def built(li):
     return bool(li.cstruct.q1code)
 
 
-def gid_of(rf, ls):
-    ri = np.where(rf == ord("A"), 0, np.where(rf == ord("N"), 1, 2))
-    return (ri * 2 + np.where(ls == ord("F"), 0, 1)).astype(np.uint32)
-
-
 def decode(li):
     """numpy decode of the code column through the descriptor."""
     d = li.cstruct.q1desc
@@ -101,22 +98,6 @@ def assert_round_trip(li):
         assert (np.diff(dic.astype(object)) > 0).all()   # sorted, distinct
 
 
-def host_cols(n, seed=7, **over):
-    """A small Q1-shaped host table; keyword arguments replace columns."""
-    rng = np.random.default_rng(seed)
-    cols = {
-        "l_quantity": rng.integers(1, 51, n).astype(np.float64),
-        "l_extendedprice": rng.uniform(900.0, 105000.0, n),
-        "l_discount": rng.integers(0, 11, n) / 100.0,
-        "l_tax": rng.integers(0, 9, n) / 100.0,
-        "l_returnflag": rng.choice(np.frombuffer(b"ANR", np.uint8), n),
-        "l_linestatus": rng.choice(np.frombuffer(b"FO", np.uint8), n),
-        "l_shipdate": rng.integers(0, 2526, n).astype(np.int32),
-    }
-    cols.update(over)
-    return cols
-
-
 N_CRAFT = 4099
 
 
@@ -144,6 +125,24 @@ def test_coded_vs_raw(ex, n):
         assert_same(run_default(ex, li, cutoff), ref, f"default n={n}")
     assert run_variant(li, base - 1, 3)[1].sum() == 0
     assert run_variant(li, dmax, 3)[1].sum() == n
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2])
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 7, 8, 9, 255, 513, 4099])
+def test_raw_variants_small_n(ex, n, variant):
+    """The raw-column kernels (the fallback of every table whose code column
+    does not build) against an exactly summed host reference: every n % 2
+    and n % 4, n below one vector, one row past a block multiple. At most
+    4099 non-negative terms per sum, so any summation order is within
+    n * 2^-53 ~ 4.6e-13 of the exact sum: inside REL_VARIANTS."""
+    cols = host_cols(n)
+    li = ex.GpuLineitem.from_host(cols, with_orderkey=False)
+    for cutoff in (1200, -2**31, 2**31 - 1):
+        got = run_variant(li, cutoff, variant)
+        assert_same(got, ref_q1_partial(cols, cutoff),
+                    f"v{variant} n={n} cut={cutoff}")
+        if cutoff != 1200:
+            assert got[1].sum() == (0 if cutoff < 0 else n)
 
 
 def test_coded_vs_oracle(ex, ora):

@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import q1_ref
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
@@ -132,21 +134,9 @@ def assert_not_built(ex, li):
         assert variant_status(li, CUTOFF, v)[0] == 3
 
 
-def host_cols(n, seed=7, **over):
-    """A small Q1-shaped host table with two-decimal money prices; keyword
-    arguments replace columns."""
-    rng = np.random.default_rng(seed)
-    cols = {
-        "l_quantity": rng.integers(1, 51, n).astype(np.float64),
-        "l_extendedprice": rng.integers(90_000, 10_500_001, n) / 100.0,
-        "l_discount": rng.integers(0, 11, n) / 100.0,
-        "l_tax": rng.integers(0, 9, n) / 100.0,
-        "l_returnflag": rng.choice(np.frombuffer(b"ANR", np.uint8), n),
-        "l_linestatus": rng.choice(np.frombuffer(b"FO", np.uint8), n),
-        "l_shipdate": rng.integers(0, 2526, n).astype(np.int32),
-    }
-    cols.update(over)
-    return cols
+def host_cols(n, **over):
+    """q1_ref.host_cols with two-decimal money prices."""
+    return q1_ref.host_cols(n, money=True, **over)
 
 
 def staged(ex, **over):

@@ -2,9 +2,10 @@
 """Within-probe interleaved A/B of the Q1 kernel variants (guide §5.4 rule 24):
 N rounds × variants interleaved in one process; reports median/min ms and
 checks result parity across variants. Variants 0-2 read the raw columns
-(38 B/row), 3 to 5 the staged code column + l_extendedprice (12 B/row), 6 and
-7 the code column + the packed price column (8 B/row); the bandwidth printed
-is each variant's own physical bytes over its time.
+(38 B/row; k_q1_raw<2,false>, <4,false>, <4,true> of csrc/otbx_q1.hip), 3 to
+5 the staged code column + l_extendedprice (12 B/row; k_q1_coded), 6 and 7
+the code column + the packed price column (8 B/row; k_q1_coded<.., true>);
+the bandwidth printed is each variant's own physical bytes over its time.
 
 usage: q1_ab.py [SF [ROUNDS [VARIANT ...]]]   (default 100, 8, all eight)"""
 import ctypes as C
