@@ -52,7 +52,13 @@
  *                            sorted input: AGG_SORTED / AGG_PLAIN
  *                            (agg_retrieve_direct, nodeAgg.c:2249) with
  *                            several count / sum / min / max per group
- *   otbx_filter_sel        — ExecScan/ExecQual for any qual shape: a CNF of
+ *   otbx_ordered_agg       — the aggregates that sort their input inside
+ *                            each group: agg(DISTINCT x)
+ *                            (process_ordered_aggregate_single,
+ *                            nodeAgg.c:888) and percentile_disc /
+ *                            percentile_cont / mode() WITHIN GROUP
+ *                            (utils/adt/orderedsetaggs.c)
+ *   otbx_filter_sel       — ExecScan/ExecQual for any qual shape: a CNF of
  *                            typed, nullable comparisons (execScan.c:140,
  *                            EEOP_QUAL execExprInterp.c:919) → the ordered
  *                            selection vector the other operators gather by
@@ -1072,6 +1078,117 @@ otbx_status otbx_group_agg(const otbx_sortspec *spec,   /* the GROUP BY keys, 0.
                            int64_t *first_row_dev,      /* capacity n; may be NULL */
                            int64_t *ngroups_dev,        /* int64[1], required      */
                            void *stream);
+
+/* ---- GPU DISTINCT and ordered-set aggregates over sorted input ----
+ * The aggregates that sort their own input inside each group: agg(DISTINCT x)
+ * (process_ordered_aggregate_single, executor/nodeAgg.c:888: sort, then skip
+ * every row equal to its predecessor) and the ordered-set aggregates
+ * percentile_disc / percentile_cont / mode() WITHIN GROUP (ORDER BY x)
+ * (utils/adt/orderedsetaggs.c: sort, then pick or interpolate a row). Here
+ * the sort is done ONCE for all groups: the caller sorts on (GROUP BY keys,
+ * x) with otbx_sort_perm, and every aggregate is one pass over that
+ * permutation.
+ *
+ * INPUTS AND GROUPING
+ *   - spec->nkeys == ngroup + 1, 0 <= ngroup <= 7. key[0..ngroup-1] are the
+ *     GROUP BY keys; key[ngroup] is the ONE argument column x that all calls
+ *     share. Its type, null mask, DESC and NULLS FIRST flags are the sort
+ *     key's: "ORDER BY x DESC NULLS FIRST" is a flag pair, not another call.
+ *   - perm_dev is what otbx_sort_perm(spec, n, limit 0) returned; NULL means
+ *     identity. An entry outside [0, n) is clamped.
+ *   - Group g is the g-th run of equal GROUP BY keys. The numbering,
+ *     first_row_dev and *ngroups_dev are exactly what otbx_group_agg gives
+ *     for the first ngroup keys of spec and the same perm_dev, so a target
+ *     list can take count(DISTINCT x) from here and sum(y) from
+ *     otbx_group_agg side by side, from one sort.
+ *   - ngroup == 0 is AGG_PLAIN: one group over all rows. With n == 0 it
+ *     still emits one row: COUNT_DISTINCT 0, everything else NULL,
+ *     first_row = -1. ngroup > 0 and n == 0: *ngroups_dev = 0, nothing else
+ *     is written.
+ *   - Equality everywhere is that of the sort's normalised key: NULL equals
+ *     NULL, every NaN equals every NaN, -0.0 == +0.0, and the value stored
+ *     under a NULL is ignored.
+ *   - ncalls == 0 is legal and needs first_row_dev: DISTINCT on the GROUP BY
+ *     keys.
+ *
+ * NULL ARGUMENTS take part in no aggregate (the transition functions are
+ *   strict; ordered_set_transition drops NULLs). Inside a group they sit
+ *   together at the end the key's flags put them. Below, N is the number of
+ *   the group's non-NULL rows and lo the position of the first of them, so
+ *   they occupy positions lo .. lo+N-1 in the order of perm_dev.
+ *
+ * AGGREGATES ("the value at position j" is the argument of row perm_dev[j])
+ *   COUNT_DISTINCT      int64: the runs of equal non-NULL values; 0 for an
+ *                       all-NULL group. Never NULL.
+ *   SUM_DISTINCT        the sum over the FIRST POSITION of each such run,
+ *                       typed and encoded exactly as OTBX_AGG_SUM: F64 gives
+ *                       a double under the NUMERICS clause of otbx_group_agg
+ *                       (a segmented tree, deterministic; m = runs - 1);
+ *                       I32 / U8 give an exact int64; I64 gives the exact
+ *                       int128 in out / out_hi. NULL when N == 0.
+ *   PERCENTILE_DISC(p)  the value at lo + max(K, 1) - 1 with
+ *                       K = (int64)ceil(p * (double)N): the type of the
+ *                       column, the BIT PATTERN of that row
+ *                       (orderedsetaggs.c:468). NULL when N == 0.
+ *   PERCENTILE_CONT(p)  always a double. t = p * (double)(N - 1),
+ *                       f = floor(t), c = ceil(t); if f == c the value at
+ *                       lo + f, else v_f + (t - f) * (v_c - v_f), evaluated
+ *                       in exactly that order without a fused multiply-add
+ *                       (:568-594, float8_lerp :496). Integer columns
+ *                       convert as i8tod / i4tod. Bit-exact. NULL when
+ *                       N == 0.
+ *   MODE                the value at the first position of the longest run
+ *                       of equal non-NULL values; among runs of equal
+ *                       length the earliest in sort order (mode_final :1090
+ *                       takes a new mode only on ">"). Type of the column,
+ *                       bit pattern of that row. NULL when N == 0.
+ *   A NULL result stores 0 and sets out_null = 1. A NaN that the arithmetic
+ *   itself creates (SUM_DISTINCT over +Inf and -Inf, PERCENTILE_CONT between
+ *   them) is a NaN with the adder's payload; a NaN that is picked
+ *   (PERCENTILE_DISC, MODE, PERCENTILE_CONT with f == c) keeps its bits.
+ *   Several percentiles — the reference's percentile_disc(array[...]) too —
+ *   are several calls of one invocation. avg(DISTINCT x) is a finalizer over
+ *   SUM_DISTINCT and COUNT_DISTINCT. Since otbx_sort_perm is stable and the
+ *   reference's sort is not, "the row" among equal values is defined by
+ *   perm_dev: the first position of the run. That is what makes -0 / +0 and
+ *   NaN payloads reproducible bit for bit.
+ *
+ * Stream-ordered, no host synchronisation, nothing cached (otbx_finish has
+ * nothing to release); entries past *ngroups_dev are never written. Checked
+ * before any HIP call, each returning OTBX_ERR_INVALID: spec, calls or
+ * ngroups_dev NULL; ngroup outside 0..7 or nkeys != ngroup + 1; a key type
+ * code outside 0..3 or key flags outside bits 0-1; ncalls outside 0..8;
+ * ncalls == 0 with first_row_dev == NULL; func out of range; fraction below
+ * 0, above 1 or NaN on a percentile call (the reference raises "percentile
+ * value is not between 0 and 1"); out == NULL; out_null missing where the
+ * result can be NULL or present for COUNT_DISTINCT; out_hi missing for
+ * SUM_DISTINCT over I64 or present elsewhere; n < 0 or n > INT32_MAX; a NULL
+ * key column with n > 0; ws_bytes below
+ * otbx_ordered_agg_workspace_bytes(n, ncalls), or ws_dev not 16-byte
+ * aligned. The workspace function is pure host code and monotone in n. */
+enum { OTBX_OAGG_COUNT_DISTINCT = 0, OTBX_OAGG_SUM_DISTINCT,
+       OTBX_OAGG_PERCENTILE_DISC, OTBX_OAGG_PERCENTILE_CONT, OTBX_OAGG_MODE };
+typedef struct {
+    void    *out;       /* one entry per group, capacity n                      */
+    int64_t *out_hi;    /* SUM_DISTINCT over I64 only: high words of the int128 */
+    uint8_t *out_null;  /* 1 where the result is NULL; must be NULL for
+                           COUNT_DISTINCT                                       */
+    double   fraction;  /* the percentiles' p in [0, 1]; ignored elsewhere      */
+    int32_t  func;      /* OTBX_OAGG_*                                          */
+    int32_t  _pad;
+} otbx_oaggcall;        /* 40 B */
+typedef struct { int32_t ncalls; int32_t _pad; otbx_oaggcall call[OTBX_MAX_AGGS]; } otbx_oaggcalls;
+
+otbx_status otbx_ordered_agg_workspace_bytes(int64_t n, int32_t ncalls,
+                                             size_t *bytes);
+otbx_status otbx_ordered_agg(const otbx_sortspec *spec,  /* GROUP BY keys, then x */
+                             int32_t ngroup,             /* 0..7                  */
+                             const int64_t *perm_dev,    /* NULL = identity       */
+                             int64_t n, const otbx_oaggcalls *calls,
+                             void *ws_dev, size_t ws_bytes,
+                             int64_t *first_row_dev,     /* capacity n; may be NULL */
+                             int64_t *ngroups_dev,       /* int64[1], required    */
+                             void *stream);
 
 /* ---- generic GPU Filter: WHERE quals → ordered selection vector ----
  * The ExecScan / ExecQual analog (executor/execScan.c:140-363 over the

@@ -168,6 +168,26 @@ class AggCallsDev(C.Structure):
 
 assert C.sizeof(AggCallDev) == 48 and C.sizeof(AggCallsDev) == 392
 
+OAGG_FUNCS = {"count_distinct": 0, "sum_distinct": 1, "percentile_disc": 2,
+              "percentile_cont": 3, "mode": 4}   # OTBX_OAGG_*
+
+
+class OAggCallDev(C.Structure):
+    """otbx_oaggcall (include/otbx.h): one DISTINCT / ordered-set aggregate,
+    40 bytes."""
+    _fields_ = [("out", C.c_void_p), ("out_hi", C.c_void_p),
+                ("out_null", C.c_void_p), ("fraction", C.c_double),
+                ("func", C.c_int32), ("_pad", C.c_int32)]
+
+
+class OAggCallsDev(C.Structure):
+    """otbx_oaggcalls: up to 8 calls on one argument column, 328 bytes."""
+    _fields_ = [("ncalls", C.c_int32), ("_pad", C.c_int32),
+                ("call", OAggCallDev * MAX_AGGS)]
+
+
+assert C.sizeof(OAggCallDev) == 40 and C.sizeof(OAggCallsDev) == 328
+
 
 class QualTermDev(C.Structure):
     """otbx_qualterm (include/otbx.h): one comparison of a qual, 64 bytes."""
@@ -276,6 +296,8 @@ def lib():
             C.POINTER(C.c_int64)]
         _lib.otbx_filter_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_group_agg_workspace_bytes.argtypes = [i64, szp]
+        _lib.otbx_ordered_agg_workspace_bytes.argtypes = [i64, C.c_int32,
+                                                          szp]
         _lib.otbx_text_gather_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_text_rank_workspace_bytes.argtypes = [i64, szp]
         _lib.otbx_q1code_plan.argtypes = [
@@ -326,6 +348,7 @@ EXPORTED_SYMBOLS = [
     "otbx_filter_workspace_bytes", "otbx_filter_sel",
     "otbx_project",
     "otbx_group_agg_workspace_bytes", "otbx_group_agg",
+    "otbx_ordered_agg_workspace_bytes", "otbx_ordered_agg",
     "otbx_text_pred", "otbx_text_gather_workspace_bytes",
     "otbx_text_gather_offsets", "otbx_text_gather_bytes",
     "otbx_text_rank_workspace_bytes", "otbx_text_rank",

@@ -18,9 +18,10 @@ import torch
 
 from ._lib import (AGG_FUNCS, FB_CURRENT, FB_OFFSET, FB_UNBOUNDED,
                    FRAME_RANGE, FRAME_ROWS, MAX_AGGS, MAX_TEXT_CONST,
-                   MAX_TEXT_RANK_COLS, MAX_WINCALLS, TEXT_ENCODINGS, TXT_OPS,
-                   WIN_FUNCS, AggCallsDev, CustomerDev, ExprDev, FrameDev,
-                   KeysetDev, LineitemDev, OrdersDev, OtbxError, PartDev,
+                   MAX_TEXT_RANK_COLS, MAX_WINCALLS, OAGG_FUNCS, TEXT_ENCODINGS,
+                   TXT_OPS, WIN_FUNCS, AggCallsDev, CustomerDev, ExprDev,
+                   FrameDev, KeysetDev, LineitemDev, OAggCallsDev, OrdersDev,
+                   OtbxError, PartDev,
                    Q1_DICT_MAX, Q1CodeDesc, Q1PriceDesc, QualDev, SortSpecDev,
                    TextColDev, TextPredDev, TextSetDev, WinCallDev,
                    WindowOutDev, call, check, lib)
@@ -1319,6 +1320,180 @@ class GpuGroupAgg(CustomScanState):
         if self.group_agg_ms is None:
             return None
         return {"sort": self.sort_ms, "group_agg": self.group_agg_ms}
+
+
+class GpuOrderedAgg(CustomScanState):
+    """The aggregates that sort their argument inside each group:
+    agg(DISTINCT x) (process_ordered_aggregate_single, nodeAgg.c:888) and
+    percentile_disc / percentile_cont / mode() WITHIN GROUP (ORDER BY x)
+    (orderedsetaggs.c), for 0..7 GROUP BY keys and ONE argument column `arg`
+    (device tensors of dtype int64, float64, int32 or uint8, with optional
+    null masks). aggs is a list of up to 8 of
+        ("count_distinct",) | ("sum_distinct",)
+        | ("percentile_disc", p) | ("percentile_cont", p) | ("mode",)
+    with 0 <= p <= 1; several percentiles (percentile_disc(array[...])) are
+    several entries. arg_descending / arg_nulls_first are the ORDER BY flags
+    of the argument (arg_nulls_first=None takes the SQL default of the
+    direction). Runs GpuSort on keys + [arg] unless a `perm` sorted that way
+    is passed, then otbx_ordered_agg. Yields ONE tuple, a dict shaped like
+    GpuGroupAgg's:
+        "ngroups", "first_row", "keys"   as GpuGroupAgg yields them — the
+                    same group numbering, so GpuGroupAgg(keys, ..., perm=
+                    row["perm"]) gives the ordinary aggregates of the same
+                    target list, side by side, from the one sort
+        "aggs"      [(values, nulls or None)] cut to ngroups, in list order;
+                    sum_distinct over int64 yields (lo, hi, nulls), see
+                    int128_sums(); percentile_disc and mode have arg's dtype
+                    and the chosen row's bit pattern, percentile_cont is
+                    float64, count_distinct int64 without nulls
+        "perm"      the permutation used
+    avg(DISTINCT x) is avg_f64 / dec_avg over sum_distinct and
+    count_distinct. A text argument needs no kernel of its own: rank the
+    column with GpuText.rank, pass the codes as `arg`, and TextRank.decode
+    turns percentile_disc / mode results back into strings (count_distinct
+    of the codes is count(DISTINCT name)). Contract in include/otbx.h
+    (otbx_ordered_agg)."""
+
+    def __init__(self, keys, arg, aggs, arg_nulls=None, arg_descending=False,
+                 arg_nulls_first=False, descending=None, nulls_first=None,
+                 key_nulls=None, perm=None, n=None):
+        super().__init__()
+        self.keys = list(keys)
+        nk = len(self.keys)
+        if nk > 7:
+            raise OtbxError(3, "ordered agg: at most 7 keys")
+        self.nulls = [None] * nk if key_nulls is None else list(key_nulls)
+        if len(self.nulls) != nk:
+            raise OtbxError(3, "ordered agg: one key_nulls entry per key")
+        self.flags = sort_flags(nk, descending, nulls_first) + \
+            sort_flags(1, [arg_descending], [arg_nulls_first])
+        if not isinstance(arg, torch.Tensor):
+            raise OtbxError(3, "ordered agg: the argument is a device tensor")
+        for k in self.keys + [arg]:
+            if k.dtype not in _SORT_TYPE:
+                raise OtbxError(
+                    3, f"ordered agg: unsupported dtype {k.dtype}")
+        self.arg, self.arg_nulls = arg, arg_nulls
+        self.aggs = []
+        for a in aggs:
+            a = tuple(a)
+            if not a or a[0] not in OAGG_FUNCS:
+                raise OtbxError(3, f"ordered agg: unknown aggregate {a[:1]}")
+            func, p = a[0], 0.0
+            if func in ("percentile_disc", "percentile_cont"):
+                if len(a) != 2:
+                    raise OtbxError(3, f"ordered agg: {func} needs a fraction")
+                p = float(a[1])
+                if not 0.0 <= p <= 1.0:   # a NaN fails too
+                    raise OtbxError(3, f"percentile value {p:g} is not "
+                                       "between 0 and 1")
+            elif len(a) != 1:
+                raise OtbxError(3, f"ordered agg: {func} takes no parameter")
+            self.aggs.append((func, p))
+        if len(self.aggs) > MAX_AGGS:
+            raise OtbxError(3, "ordered agg: at most 8 aggregates")
+        self.n = len(arg) if n is None else int(n)
+        for k in self.keys + [arg]:
+            if len(k) != self.n:
+                raise OtbxError(3, "ordered agg: columns differ in length")
+        self.perm = perm
+        self.sort_ms = None
+        self.ordered_agg_ms = None
+
+    def spec(self):
+        sp = SortSpecDev()
+        cols = self.keys + [self.arg]
+        nulls = self.nulls + [self.arg_nulls]
+        sp.nkeys = len(cols)
+        for c, k in enumerate(cols):
+            sp.key[c].col = k.data_ptr()
+            nt = nulls[c]
+            sp.key[c].nulls = nt.data_ptr() if nt is not None else None
+            sp.key[c].type = _SORT_TYPE[k.dtype]
+            sp.key[c].flags = self.flags[c]
+        return sp
+
+    def _run(self):
+        L = lib()
+        n = self.n
+        self.sort_ms = 0.0
+        perm = self.perm
+        if perm is None:
+            srt = GpuSort(self.keys + [self.arg],
+                          nulls=self.nulls + [self.arg_nulls])
+            srt.flags = list(self.flags)
+            srt.BeginCustomScan()
+            perm = srt.ExecCustomScan()
+            srt.EndCustomScan()
+            self.sort_ms = srt.sort_ms
+        sp = self.spec()
+        ws_bytes = C.c_size_t(0)
+        check(L.otbx_ordered_agg_workspace_bytes(
+            C.c_int64(n), C.c_int32(len(self.aggs)), C.byref(ws_bytes)),
+            "otbx_ordered_agg_workspace_bytes")
+        ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8,
+                         device="cuda")
+        cap = max(n, 1)
+
+        def new(dtype):
+            return torch.empty(cap, dtype=dtype, device="cuda")
+
+        adt = self.arg.dtype
+        calls = OAggCallsDev()
+        calls.ncalls = len(self.aggs)
+        outs = []
+        for i, (func, p) in enumerate(self.aggs):
+            oc = calls.call[i]
+            oc.func = OAGG_FUNCS[func]
+            oc.fraction = p
+            if func == "count_distinct":
+                o = (new(torch.int64),)
+            elif func == "sum_distinct" and adt == torch.int64:
+                o = (new(torch.int64), new(torch.int64), new(torch.uint8))
+                oc.out_hi = o[1].data_ptr()
+            elif func == "sum_distinct":
+                o = (new(torch.float64 if adt == torch.float64
+                         else torch.int64), new(torch.uint8))
+            elif func == "percentile_cont":
+                o = (new(torch.float64), new(torch.uint8))
+            else:
+                o = (new(adt), new(torch.uint8))
+            oc.out = o[0].data_ptr()
+            if len(o) > 1:
+                oc.out_null = o[-1].data_ptr()
+            outs.append(o)
+        first = new(torch.int64)
+        ng = torch.zeros(1, dtype=torch.int64, device="cuda")
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        call("otbx_ordered_agg", C.byref(sp), C.c_int32(len(self.keys)),
+             C.c_void_p(perm.data_ptr()) if perm is not None and n > 0
+             else None,
+             C.c_int64(n), C.byref(calls), C.c_void_p(ws.data_ptr()),
+             C.c_size_t(ws_bytes.value), C.c_void_p(first.data_ptr()),
+             C.c_void_p(ng.data_ptr()), _stream())
+        ev1.record()
+        ngroups = int(ng.cpu().item())
+        self.ordered_agg_ms = ev0.elapsed_time(ev1)
+        first = first[:ngroups]
+        keys = []
+        for k, m in zip(self.keys, self.nulls):
+            if ngroups == 0:
+                keys.append((k[:0], None if m is None else m[:0]))
+            else:
+                keys.append((gather(k, first),
+                             None if m is None else gather(m, first)))
+        self.perm = perm
+        return [{"ngroups": ngroups, "first_row": first, "keys": keys,
+                 "aggs": [tuple(t[:ngroups] for t in o) if len(o) > 1
+                          else (o[0][:ngroups], None) for o in outs],
+                 "perm": perm}]
+
+    def explain(self):
+        if self.ordered_agg_ms is None:
+            return None
+        return {"sort": self.sort_ms, "ordered_agg": self.ordered_agg_ms}
 
 
 def int128_sums(lo, hi, nulls=None):

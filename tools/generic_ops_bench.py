@@ -31,6 +31,13 @@ distinct from the fused query pipelines.
                                    its sort, next to otbx_window, the hash
                                    aggregate and a plain-torch composition
                                    (writes profiles/groupagg_ops.txt, or PATH)
+  generic_ops_bench.py --ordagg [--rows N] [--out PATH]
+                                   otbx_ordered_agg at 600 M rows (or N) and
+                                   4 / 1 M / 100 M groups, timed apart from
+                                   its sort, next to the two-call
+                                   otbx_group_agg route to count(DISTINCT),
+                                   otbx_group_agg set A and plain torch
+                                   (writes profiles/ordagg_ops.txt, or PATH)
   generic_ops_bench.py --text [--rows N[,N..]] [--out PATH]
                                    otbx_text_pred (LIKE / compare, staged and
                                    forced-direct) and the text gather on
@@ -713,6 +720,199 @@ def bench_groupagg(out_path, n=600_000_000):
             f"{ib*1e3:8.2f} ms  worst {iw*1e3:8.2f} ms; the gathers through "
             f"perm cost {(ga_best-ib)*1e3:.2f} ms of set A")
         del ga, pre, pv, srt, key, res, ga_cnt, ga_sum, xc, xs
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+class _OrdAggCall:
+    """otbx_ordered_agg on a permutation sorted on (key, x), buffers
+    allocated once. calls: [(func,) | (func, fraction)]"""
+
+    def __init__(self, srt, ngroup, arg, calls):
+        from opentenbase_amd._lib import OAGG_FUNCS, OAggCallsDev
+        self.n, self.ngroup = srt.n, ngroup
+        self.spec, self.perm, self.stream = srt.spec, srt.perm, srt.stream
+        wsb = C.c_size_t(0)
+        lib().otbx_ordered_agg_workspace_bytes(
+            C.c_int64(self.n), C.c_int32(len(calls)), C.byref(wsb))
+        self.wsb = wsb.value
+        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device="cuda")
+        self.calls = OAggCallsDev()
+        self.calls.ncalls = len(calls)
+        self.outs = []
+        self.group_bytes = 8                              # first_row
+        funcs = [c[0] for c in calls]
+        for i, c in enumerate(calls):
+            oc = self.calls.call[i]
+            oc.func = OAGG_FUNCS[c[0]]
+            oc.fraction = c[1] if len(c) > 1 else 0.0
+            wide = c[0] == "sum_distinct" and arg.dtype == torch.int64
+            dt = torch.int64 if c[0] == "count_distinct" or wide else (
+                torch.float64 if c[0] == "percentile_cont" else arg.dtype)
+            o = [torch.empty(self.n, dtype=dt, device="cuda")]
+            oc.out = o[0].data_ptr()
+            if wide:
+                o.append(torch.empty(self.n, dtype=torch.int64, device="cuda"))
+                oc.out_hi = o[1].data_ptr()
+            if c[0] != "count_distinct":
+                o.append(torch.empty(self.n, dtype=torch.uint8, device="cuda"))
+                oc.out_null = o[-1].data_ptr()
+            self.outs.append(o)
+            self.group_bytes += sum(t.element_size() for t in o)
+            # the per-group value reads: perm entry + value
+            reads = {"percentile_disc": 1, "percentile_cont": 2,
+                     "mode": 1}.get(c[0], 0)
+            self.group_bytes += reads * (8 + arg.element_size())
+        # flag passes: one per kind of aggregate present
+        self.flag_passes = sum((
+            any(f in ("count_distinct", "percentile_disc", "percentile_cont")
+                for f in funcs), "mode" in funcs, "sum_distinct" in funcs))
+        self.sum_distinct = "sum_distinct" in funcs
+        self.arg_bytes = arg.element_size()
+        self.first = torch.empty(self.n, dtype=torch.int64, device="cuda")
+        self.ng = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+    def __call__(self):
+        call("otbx_ordered_agg", C.byref(self.spec), C.c_int32(self.ngroup),
+             C.c_void_p(self.perm.data_ptr()), C.c_int64(self.n),
+             C.byref(self.calls), C.c_void_p(self.ws.data_ptr()),
+             C.c_size_t(self.wsb), C.c_void_p(self.first.data_ptr()),
+             C.c_void_p(self.ng.data_ptr()), self.stream)
+
+    def algorithmic_bytes(self, key_bytes, ngroups, nruns):
+        """the boundary pass reads perm, gathers the keys and
+        the argument once and writes one flag byte; first_row reads the
+        flags; every kind of aggregate reads the flags once; sum_distinct
+        reads perm and the value once per RUN; per group first_row, the
+        outputs and the percentile / mode gathers"""
+        per_row = 8 + key_bytes + self.arg_bytes + 1 + 1 + self.flag_passes
+        per_run = (8 + self.arg_bytes) if self.sum_distinct else 0
+        return self.n * per_row + nruns * per_run + ngroups * self.group_bytes
+
+
+def _torch_count_distinct(key, x, perm):
+    """what a caller would write without the operator: gather both columns,
+    mark where the pair changes, and count the marks per key run (a cumsum
+    read at the run ends). torch.unique_consecutive has no pair form short
+    of stacking the columns, and torch.quantile no grouped form: the
+    percentiles and the mode have no plain-torch comparator here."""
+    sk, sx = key[perm], x[perm]
+    n = len(perm)
+    newk = torch.ones(n, dtype=torch.bool, device="cuda")
+    newk[1:] = sk[1:] != sk[:-1]
+    newp = newk.clone()
+    newp[1:] |= sx[1:] != sx[:-1]
+    del sk, sx
+    starts = newk.nonzero().flatten()
+    ends = torch.cat([starts[1:], torch.tensor([n], device="cuda")])
+    tot = torch.cumsum(newp, 0)[ends - 1]
+    cnt = tot.clone()
+    cnt[1:] -= tot[:-1]
+    return cnt
+
+
+def bench_ordagg(out_path, n=600_000_000):
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    say("# tools/generic_ops_bench.py --ordagg — best / worst of 5 wall time "
+        "after torch.cuda.synchronize(), columns staged")
+    say("# GROUP BY one i64 key, argument x = f64 with 1000 integer values; "
+        "the sort on (key, x) and otbx_ordered_agg are timed apart; set C = "
+        "{count_distinct}, set S = {count_distinct, sum_distinct}, set P = "
+        "{percentile_disc 0.5, percentile_cont 0.5, mode}")
+    g = torch.Generator(device="cuda").manual_seed(13)
+    x = torch.randint(0, 1000, (n,), dtype=torch.int64, device="cuda",
+                      generator=g).to(torch.float64)
+    sets = (("C", [("count_distinct",)]),
+            ("S", [("count_distinct",), ("sum_distinct",)]),
+            ("P", [("percentile_disc", 0.5), ("percentile_cont", 0.5),
+                   ("mode",)]))
+
+    class _On:
+        pass
+    for groups in (4, 1_000_000, 100_000_000):
+        key = torch.randint(0, groups, (n,), dtype=torch.int64, device="cuda",
+                            generator=g)
+        srt = _SortCall([key, x], [False, False])
+        sb, sw = _best_of_5(srt)
+        say(f"groups={groups:_} n={n:_}: sort on (key, x) best {sb*1e3:8.2f} "
+            f"ms  worst {sw*1e3:8.2f} ms")
+        best = {}
+        cd = None
+        for tag, calls in sets:
+            oa = _OrdAggCall(srt, 1, x, calls)
+            ob, ow = _best_of_5(oa)
+            ng = int(oa.ng.cpu().item())
+            if cd is None:
+                cd = oa.outs[0][0][:ng].clone()
+                nruns = int(cd.sum().item())
+            nbytes = oa.algorithmic_bytes(8, ng, nruns)
+            tbs = nbytes / ob / 1e12
+            say(f"  set {tag}: otbx_ordered_agg best {ob*1e3:8.2f} ms  worst "
+                f"{ow*1e3:8.2f} ms (spread {(ow-ob)/ob*100:.1f} %)  ngroups="
+                f"{ng:_} runs={nruns:_}  {nbytes/1e9:.1f} GB algorithmic  "
+                f"{tbs:5.2f} TB/s = {tbs*1e12/COPY_CEILING*100:4.1f} % of the "
+                f"6.29 TB/s copy ceiling")
+            best[tag] = ob
+            del oa
+            torch.cuda.empty_cache()
+        # (a) the only route before this operator: DISTINCT on (key, x) with
+        # otbx_group_agg, gather the keys, count per key — same sort
+        pairs = _GroupAggCall(srt, [])
+        one = _On()
+        one.n, one.stream = n, srt.stream
+
+        def two_step():
+            pairs()
+            npairs = int(pairs.ng.cpu().item())
+            pk = ex.gather(key, pairs.first[:npairs])
+            one.n, one.perm = npairs, None
+            one.spec = ex.GpuSort([pk]).spec()
+            cnt = _GroupAggCall(one, [("count_star", None)])
+            cnt()
+            return cnt
+        ab, aw = _best_of_5(two_step)
+        cnt = two_step()
+        torch.cuda.synchronize()
+        ng2 = int(cnt.ng.cpu().item())
+        same = ng2 == len(cd) and bool(torch.equal(cnt.outs[0][0][:ng2], cd))
+        say(f"  (a) two otbx_group_agg calls (DISTINCT on (key, x), gather, "
+            f"count per key; buffers allocated inside): best {ab*1e3:8.2f} ms "
+            f" worst {aw*1e3:8.2f} ms; two-step / ordered_agg (set C) time "
+            f"ratio: {ab/best['C']:.2f}; same counts: {same}")
+        del pairs, cnt
+        torch.cuda.empty_cache()
+        # (b) one boundary pass + one aggregate that gathers a value column
+        one.n, one.perm = n, srt.perm
+        one.spec = ex.GpuSort([key]).spec()
+        ga = _GroupAggCall(one, [("count_star", None), ("sum", x)])
+        gb, gw = _best_of_5(ga)
+        say(f"  (b) otbx_group_agg set A {{count_star, sum f64}} on the same "
+            f"permutation: best {gb*1e3:8.2f} ms  worst {gw*1e3:8.2f} ms; "
+            f"ordered_agg / group_agg (set A) time ratio: C "
+            f"{best['C']/gb:.2f}, S {best['S']/gb:.2f}, P {best['P']/gb:.2f}")
+        del ga
+        torch.cuda.empty_cache()
+        # (c) plain torch, count_distinct only
+        try:
+            tb, tw = _best_of_5(lambda: _torch_count_distinct(key, x,
+                                                              srt.perm))
+            tc = _torch_count_distinct(key, x, srt.perm)
+            say(f"  (c) plain torch count(DISTINCT) (gather, pair-change "
+                f"marks, cumsum at the run ends): best {tb*1e3:8.2f} ms  "
+                f"worst {tw*1e3:8.2f} ms; torch / ordered_agg (set C) time "
+                f"ratio: {tb/best['C']:.2f}; same counts: "
+                f"{bool(torch.equal(tc, cd))}")
+            del tc
+        except RuntimeError as e:
+            say(f"  (c) plain torch composition failed: {str(e)[:120]}")
+        del srt, key, cd
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as f:
@@ -1699,6 +1899,16 @@ if __name__ == "__main__":
             out_path = sys.argv[sys.argv.index("--out") + 1]
         bench_winframe(out_path, _sizes_arg("--rows", [600_000_000])[0],
                        _sizes_arg("--ab-rows", [200_000_000])[0])
+        sys.exit(0)
+    if "--ordagg" in sys.argv:
+        repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        out_path = os.path.join(repo, "profiles", "ordagg_ops.txt")
+        if "--out" in sys.argv:
+            out_path = sys.argv[sys.argv.index("--out") + 1]
+        rows = 600_000_000
+        if "--rows" in sys.argv:
+            rows = int(sys.argv[sys.argv.index("--rows") + 1])
+        bench_ordagg(out_path, rows)
         sys.exit(0)
     if "--groupagg" in sys.argv:
         repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
